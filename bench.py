@@ -24,12 +24,18 @@ process holds exactly one RCCL communicator.  The run fails (exit 3, no
 JSON) if any frame hit max_pts, the candidate capacity overflowed, or a slab
 exceeded its capacity.
 
-Rank 0 prints ONE JSON line (the driver's contract), with a `roofline` object
-for the Hessian stage (HIP events on the detector's stream; algorithmic
-bytes = integral image read once + valid responses written), an `exchange`
-object (all-gather bytes and time per step; at N = 1 a 1-rank RCCL
-all-gather of the real slab) and a `cpu_baseline` object (the oracle/ CPU
-restatement on a bounded sample of the same frames, rank 0 at N = 1 only).
+Rank 0 prints ONE JSON line (the driver's contract).  A plain run sets up,
+warms up, times --steps steps, checks that nothing was truncated, writes the
+last step's outputs when --dump-outputs DIR is given (dump_outputs) and
+prints the headline figure (`value`, `ms_per_step`), the keypoint rates and,
+at N > 1, the `exchange` object (all-gather bytes and time per step).  With
+--full the line also carries, from runs of their own after the timed region,
+a `roofline` object for the Hessian stage (HIP events on the detector's
+stream; algorithmic bytes = integral image read once + valid responses
+written), the serial per-stage times, at N = 1 an `exchange` object (a 1-rank
+RCCL all-gather of the real slab), `exchange_proxy` (--exchange-proxy) and a
+`cpu_baseline` object (the oracle/ CPU restatement on a bounded sample of the
+same frames, rank 0 at N = 1 only).
 """
 from __future__ import annotations
 
@@ -259,26 +265,37 @@ def main():
     ap.add_argument("--slab-headroom", type=float, default=1.10,
                     help="fixed per-rank slab capacity = max over ranks of the warm-up slab x this")
     ap.add_argument("--no-exchange-probe", action="store_true",
-                    help="N = 1: skip the 1-rank RCCL all-gather of the real slab")
+                    help="--full, N = 1: skip the 1-rank RCCL all-gather of the real slab")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="compute each batch's integral beside its own Hessian instead of beside the previous "
                          "batch's describe (surfhip_detect_batch_next)")
     ap.add_argument("--exchange-proxy", type=int, default=0, metavar="N",
-                    help="N = 1 only: after the timed region, time the step again with the HBM traffic an N-rank "
+                    help="--full, N = 1 only: after the timed region, time the step again with the HBM traffic an N-rank "
                          "all-gather would put on this GPU each step ((N-1) x slab bytes copied D2D on a comm "
                          "stream beside compute), for --gather full and points (SURVEY 8e; DESIGN.md 5)")
     ap.add_argument("--cpu-frames", type=int, default=128, help="frames per CPU baseline chunk")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline wall-time budget")
     ap.add_argument("--cpu-threads", type=int, default=0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-stream-peak", action="store_true", help="skip the measured HBM stream rates")
-    ap.add_argument("--no-profile", action="store_true", help="no HIP events in the timed region")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-stream-peak", action="store_true", help="--full: skip the measured HBM stream rates")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the serial per-stage pass (HIP events between the stages)")
     ap.add_argument("--pmc-json", default=None)
     ap.add_argument("--hessian-only", action="store_true",
                     help="time only the Hessian stage (for rocprofv3 --pmc passes)")
     ap.add_argument("--with-integral", action="store_true",
                     help="with --hessian-only: run the integral before every Hessian launch")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline figure: the Hessian "
+                         "roofline (in-step and serial stage times, measured HBM stream rates), the serial "
+                         "per-stage times, the N = 1 exchange probe and --exchange-proxy, and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy "
+                         "(see dump_outputs)")
     args = ap.parse_args()
+    if args.exchange_proxy and not args.full:
+        ap.error("--exchange-proxy is a --full measurement")
+    if args.dump_outputs and args.hessian_only:
+        ap.error("--dump-outputs writes the detect+describe outputs; --hessian-only computes none")
     if args.max_pts <= 0:
         args.max_pts = 65536 if args.width * args.height <= 1920 * 1088 else 262144
     if args.gpus < 1:
@@ -333,7 +350,8 @@ def run_rank(args):
     d_pts = torch.empty(B * args.max_pts * 48, dtype=torch.uint8, device=dev)
     d_desc = torch.empty(B * args.max_pts * nf, dtype=torch.float32, device=dev)
     d_cnt = torch.zeros(B, dtype=torch.int32, device=dev)
-    profile = not args.no_profile
+    full = args.full
+    profile = full and not args.no_profile
     # the timed loop runs unprofiled (the detector then overlaps the integral
     # with the u8 Hessian kernels on a side stream); stage times come from a
     # separate serial pass afterwards
@@ -477,20 +495,6 @@ def run_rank(args):
     timing[0] = False
     if world > 1:
         elapsed = float(allreduce_max(elapsed, torch.float64))
-    # The roofline's launch time: the same pipelined steps again (after the
-    # timed region, so its HIP events cannot perturb `value` -- three event
-    # records per step cost a latency-bound 1-frame step ~0.1 ms), each
-    # Hessian stage bracketed from its fork to the end of its last kernel on
-    # either stream
-    hess_instep = []
-    if not args.hessian_only:
-        det.time_hessian(True)
-        for i in range(min(args.steps, 32)):
-            run_batch()
-        torch.cuda.synchronize(dev)
-        hess_instep = det.hessian_times()
-        det.time_hessian(False)
-
     # no truncation anywhere: a frame at max_pts, a candidate-capacity
     # overflow or a slab beyond the agreed capacity invalidates the run.  The
     # counts, the truncation flag and the slab flags are read from the last
@@ -555,6 +559,23 @@ def run_rank(args):
     else:
         kp_total_batch = kp_per_batch
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, surf, d_pts, d_desc, counts, args.max_pts, nf, rank, world)
+
+    # The roofline's launch time: the same pipelined steps again (after the
+    # timed region, so its HIP events cannot perturb `value` -- three event
+    # records per step cost a latency-bound 1-frame step ~0.1 ms), each
+    # Hessian stage bracketed from its fork to the end of its last kernel on
+    # either stream
+    hess_instep = []
+    if full and not args.hessian_only:
+        det.time_hessian(True)
+        for i in range(min(args.steps, 32)):
+            run_batch()
+        torch.cuda.synchronize(dev)
+        hess_instep = det.hessian_times()
+        det.time_hessian(False)
+
     stage_acc = {}
     # per-stage times: a short serial pass with HIP events between the stages
     nprof = min(args.steps, 3)
@@ -569,44 +590,42 @@ def run_rank(args):
     # the Hessian stage alone (events on the detector's stream; all its
     # kernels in series, nothing beside them), after one integral of the same
     # frames: the serial figure, reported next to the in-step one
-    ev0 = torch.cuda.Event(enable_timing=True)
-    ev1 = torch.cuda.Event(enable_timing=True)
-    if not args.hessian_only:
-        det.run_integral(d_frames.data_ptr(), B, pitch, H * pitch)
-    ev0.record(stream)
-    for _ in range(args.steps):
-        det.run_hessian(B)
-    ev1.record(stream)
-    torch.cuda.synchronize(dev)
-    hess_serial_ms = ev0.elapsed_time(ev1) / args.steps
-    hess_ms = float(np.mean(hess_instep)) if hess_instep else hess_serial_ms
+    hess_serial_ms = hess_ms = None
+    if full:
+        ev0 = torch.cuda.Event(enable_timing=True)
+        ev1 = torch.cuda.Event(enable_timing=True)
+        if not args.hessian_only:
+            det.run_integral(d_frames.data_ptr(), B, pitch, H * pitch)
+        ev0.record(stream)
+        for _ in range(args.steps):
+            det.run_hessian(B)
+        ev1.record(stream)
+        torch.cuda.synchronize(dev)
+        hess_serial_ms = ev0.elapsed_time(ev1) / args.steps
+        hess_ms = float(np.mean(hess_instep)) if hess_instep else hess_serial_ms
 
     # N = 1: what this rank's exchange would move -- a 1-rank RCCL all-gather
     # (libsurfcomm) of the real slab, both modes, after the timed region
     probe = None
-    if world == 1 and not args.hessian_only and not args.no_exchange_probe:
+    if full and world == 1 and not args.hessian_only and not args.no_exchange_probe:
         with _StdoutToStderr():
             probe = exchange_probe(surf, torch, det, dev, stream, d_pts, d_desc, d_cnt, B, nf)
 
     proxy = None
-    if world == 1 and args.exchange_proxy > 1 and not args.hessian_only:
+    if full and world == 1 and args.exchange_proxy > 1 and not args.hessian_only:
         proxy = exchange_proxy(surf, torch, det, dev, stream, run_batch, d_pts, d_desc, d_cnt, B, args.exchange_proxy,
                                args.steps, 1e3 * elapsed / args.steps)
 
     peaks = None
-    if rank == 0 and not args.no_stream_peak:
+    if full and rank == 0 and not args.no_stream_peak:
         peaks = stream_peaks(surf, torch, dev, stream)
 
     frames_total = world * B * args.steps
     value = frames_total / elapsed
     result = None
     if rank == 0:
-        hb = det.hessian_bytes_per_frame() * B
-        achieved = hb / (hess_ms * 1e-3) / 1e9
-        traffic, traffic_tag = pmc_traffic(args)
-        kern = det.hessian_kernels()
-        hp = hessian_profile(args, kern)
         cfg_name = config_name(args, world)
+        # the plain line: the headline figure and what describes the run
         result = {
             "metric": METRIC if (W, H) == (1920, 1080) else f"{W}x{H} frames/sec (detect+describe)",
             "value": round(value, 2),
@@ -629,6 +648,21 @@ def run_rank(args):
             "keypoints_per_s": round(kp_total_batch * args.steps / elapsed, 1),
             "keypoints_per_frame": round(kp_total_batch / (world * B), 1),
             "keypoints_per_step": kp_total_batch,
+            "gen_s": round(gen_s, 2),
+            "device": _device_info(surf, dev.index),
+        }
+        if exchanged is not None:
+            result["exchange"] = exchanged
+    if rank == 0 and full:
+        # --full: the Hessian roofline, the serial stage times, the N = 1
+        # exchange probe / proxy and the CPU baseline, measured after the
+        # timed region in runs of their own
+        hb = det.hessian_bytes_per_frame() * B
+        achieved = hb / (hess_ms * 1e-3) / 1e9
+        traffic, traffic_tag = pmc_traffic(args)
+        kern = det.hessian_kernels()
+        hp = hessian_profile(args, kern)
+        result.update({
             "stage_ms_per_step_serial": {k: round(v / nprof, 4) for k, v in stage_acc.items()},
             "roofline": {"kernel": "Hessian stage, all octaves: " + kern + ", per batch",
                          # what the committed SQ / PMC counters of this config
@@ -683,12 +717,8 @@ def run_rank(args):
                          # fraction with it added to the stage
                          **(rowseg_terms(stage_acc, nprof, hb, hess_ms)
                             if "writing the integral image" in kern else {})},
-            "gen_s": round(gen_s, 2),
-            "device": _device_info(surf, dev.index),
-        }
-        if exchanged is not None:
-            result["exchange"] = exchanged
-        elif probe is not None:
+        })
+        if exchanged is None and probe is not None:
             result["exchange"] = probe
         if proxy is not None:
             result["exchange_proxy"] = proxy
@@ -696,6 +726,7 @@ def run_rank(args):
             result["cpu_baseline"] = cpu_baseline(frames, W, H, args)
         else:
             result["cpu_baseline"] = None
+    if rank == 0:
         print(json.dumps(result), flush=True)
     if ev_desc is not None:
         det.set_describe_event(None)
@@ -706,6 +737,51 @@ def run_rank(args):
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_FIELDS = ("x", "y", "scale", "o", "strength", "laplace", "ori")
+DUMP_BUDGET_BYTES = 48 << 20
+
+
+def dump_outputs(out_dir, surf, d_pts, d_desc, counts, max_pts, nf, rank, world):
+    """--dump-outputs: what detect_batch left in the caller's buffers after the
+    last timed step, as .npy files (rank r > 0 of a multi-GPU run appends
+    `_rank<r>` to the names):
+
+      counts          float64 [B]      keypoints per frame, every frame
+      sample_frames   float64 [S]      the frames whose keypoints are written
+      points          float32 [n, 7]   DUMP_FIELDS of their SurfPoints (the i32
+                                       fields are small and exact in f32), frame
+                                       after frame in sample_frames' order, each
+                                       frame in the detector's canonical order
+      descriptors     float32 [n, nf]  the same rows' descriptors
+
+    The whole batch's descriptors run to hundreds of MB, so the frames are a
+    fixed sample: a seeded permutation of the batch, taken in order while the
+    rows fit DUMP_BUDGET_BYTES (the last frame is cut at the budget).  The
+    frames are synthetic and seeded and the pipeline is deterministic, so two
+    builds run with the same arguments write comparable files."""
+    os.makedirs(out_dir, exist_ok=True)
+    B = len(counts)
+    row_budget = DUMP_BUDGET_BYTES // (4 * (len(DUMP_FIELDS) + nf))
+    pts_rows = d_pts.view(B, max_pts * 48)
+    desc_rows = d_desc.view(B, max_pts, nf)
+    picked, pts, desc = [], [], []
+    for f in np.random.default_rng(0).permutation(B):
+        if row_budget <= 0:
+            break
+        c = min(int(counts[f]), row_budget)
+        row_budget -= c
+        picked.append(int(f))
+        p = pts_rows[f, :c * 48].cpu().numpy().view(surf.POINT_DTYPE)
+        pts.append(np.stack([p[k].astype(np.float32) for k in DUMP_FIELDS], axis=1).reshape(c, len(DUMP_FIELDS)))
+        desc.append(desc_rows[f, :c].cpu().numpy())
+    suffix = f"_rank{rank}" if world > 1 and rank > 0 else ""
+    for name, arr in (("counts", counts.astype(np.float64)),
+                      ("sample_frames", np.asarray(picked, np.float64)),
+                      ("points", np.concatenate(pts).astype(np.float32)),
+                      ("descriptors", np.concatenate(desc).astype(np.float32))):
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), arr)
 
 
 class _StdoutToStderr:

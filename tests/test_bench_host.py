@@ -46,6 +46,79 @@ def test_spawned_rank_failure_ends_the_job():
     assert time.time() - t0 < 200
 
 
+def test_full_only_options_need_full():
+    """--exchange-proxy is a --full measurement and --dump-outputs has nothing
+    to write in a --hessian-only run: both are refused before any GPU work."""
+    for extra, word in ((["--exchange-proxy", "8"], "--full"), (["--hessian-only", "--dump-outputs", "x"], "--hessian-only")):
+        r = subprocess.run([sys.executable, BENCH, "--batch", "1", "--steps", "1"] + extra,
+                           capture_output=True, text=True, timeout=120, cwd=REPO, env=_env())
+        assert r.returncode == 2 and word in r.stderr, (extra, r.returncode, r.stderr[-500:])
+
+
+def test_dump_outputs_layout(tmp_path):
+    """dump_outputs on host tensors laid out like detect_batch's buffers: every
+    frame's count, a seeded sample of frames, and exactly their first
+    `count` SurfPoints and descriptors, float32 / float64, within 64 MB."""
+    import numpy as np
+    import pytest
+    torch = pytest.importorskip("torch")
+    from conftest import load_surf_amd
+    surf = load_surf_amd()
+    b = _bench()
+    B, max_pts, nf = 5, 7, 4
+    rng = np.random.default_rng(3)
+    counts = np.array([3, 0, 7, 1, 5], np.int32)
+    pts = np.zeros((B, max_pts), surf.POINT_DTYPE)
+    for k in b.DUMP_FIELDS:
+        pts[k] = rng.integers(-50, 50, (B, max_pts)).astype(pts[k].dtype)
+    desc = rng.standard_normal((B, max_pts, nf)).astype(np.float32)
+    d_pts = torch.from_numpy(pts.view(np.uint8).reshape(-1).copy())
+    d_desc = torch.from_numpy(desc.reshape(-1).copy())
+
+    def dump(name):
+        out = tmp_path / name
+        b.dump_outputs(str(out), surf, d_pts, d_desc, counts, max_pts, nf, 0, 1)
+        return {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+
+    d = dump("a")
+    assert sorted(d) == ["counts", "descriptors", "points", "sample_frames"]
+    assert d["counts"].dtype == np.float64 and d["sample_frames"].dtype == np.float64
+    assert d["points"].dtype == np.float32 and d["descriptors"].dtype == np.float32
+    assert np.array_equal(d["counts"], counts)
+    picked = d["sample_frames"].astype(int)
+    assert sorted(picked) == list(range(B))                   # the budget holds this whole batch
+    want_p = np.concatenate([np.stack([pts[f, :counts[f]][k].astype(np.float32) for k in b.DUMP_FIELDS], 1)
+                             for f in picked])
+    want_d = np.concatenate([desc[f, :counts[f]] for f in picked])
+    assert np.array_equal(d["points"], want_p) and np.array_equal(d["descriptors"], want_d)
+    again = dump("b")
+    assert all(np.array_equal(d[k], again[k]) for k in d)      # the sample is fixed
+    assert sum(a.nbytes for a in d.values()) <= 64 << 20
+
+
+def test_dump_outputs_budget(tmp_path, monkeypatch):
+    """A batch beyond the byte budget is cut: frames in the seeded order until
+    the rows run out, the last one truncated at the budget."""
+    import numpy as np
+    import pytest
+    torch = pytest.importorskip("torch")
+    from conftest import load_surf_amd
+    surf = load_surf_amd()
+    b = _bench()
+    B, max_pts, nf = 6, 10, 2
+    row = 4 * (len(b.DUMP_FIELDS) + nf)
+    monkeypatch.setattr(b, "DUMP_BUDGET_BYTES", 25 * row)
+    counts = np.full(B, 10, np.int32)
+    d_pts = torch.zeros(B * max_pts * 48, dtype=torch.uint8)
+    d_desc = torch.arange(B * max_pts * nf, dtype=torch.float32)
+    b.dump_outputs(str(tmp_path), surf, d_pts, d_desc, counts, max_pts, nf, 0, 1)
+    picked = np.load(tmp_path / "sample_frames.npy").astype(int)
+    desc = np.load(tmp_path / "descriptors.npy")
+    assert len(picked) == 3 and len(desc) == 25 and len(np.load(tmp_path / "points.npy")) == 25
+    full = d_desc.numpy().reshape(B, max_pts, nf)
+    assert np.array_equal(desc, np.concatenate([full[picked[0]], full[picked[1]], full[picked[2], :5]]))
+
+
 def test_config_labels():
     b = _bench()
 

@@ -20,7 +20,7 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import REPO, assert_points_equal
+from conftest import REPO, assert_points_equal, desc_l2
 from test_gpu_parity import compare_frame, gpu_run
 
 pytestmark = pytest.mark.gpu
@@ -195,7 +195,7 @@ def test_bench_spawns_its_ranks(gather):
 def test_bench_single_gpu_exchange_probe():
     """N = 1: the line carries a 1-rank RCCL all-gather of the real slab."""
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--batch", "8", "--steps", "3",
-                        "--warmup", "1", "--no-cpu"], capture_output=True, text=True, timeout=240, cwd=REPO)
+                        "--warmup", "1", "--full", "--no-cpu"], capture_output=True, text=True, timeout=240, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and lines[0].startswith("{"), r.stdout      # RCCL's banner goes to stderr
@@ -206,12 +206,50 @@ def test_bench_single_gpu_exchange_probe():
     assert ex["full"]["slab_bytes"] > ex["points"]["slab_bytes"] > 0
 
 
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path, surf, orc):
+    """A plain run prints the headline line without the --full measurements,
+    and --dump-outputs writes the last step's counts, SurfPoints and
+    descriptors: the sampled frames equal the oracle (keypoints bit for bit,
+    descriptors within 1e-4 L2)."""
+    n, w, h = 3, 320, 240
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--batch", str(n), "--width",
+                        str(w), "--height", str(h), "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=240, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{"), r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0
+    # value = frames / elapsed and ms_per_step = elapsed / steps, each rounded (2 and 4 decimals)
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 / n - 1) <= 5e-5 / d["ms_per_step"] + 0.005 / d["value"] + 1e-9
+    assert not {"roofline", "cpu_baseline", "exchange", "stage_ms_per_step_serial"} & set(d)
+    counts = np.load(tmp_path / "counts.npy")
+    picked = np.load(tmp_path / "sample_frames.npy").astype(int)
+    pts = np.load(tmp_path / "points.npy")
+    desc = np.load(tmp_path / "descriptors.npy")
+    assert counts.sum() == d["keypoints_per_step"] > 0 and sorted(picked) == list(range(n))
+    assert pts.dtype == np.float32 and desc.dtype == np.float32 and len(pts) == len(desc) == counts.sum()
+    frames = surf.synth_frames(n, w, h, surf.align_up(w, 128), first=0)
+    op = orc.make_param(4, 4.0, False, 9, 2, True, False, 4)
+    fields = ("x", "y", "scale", "o", "strength", "laplace", "ori")
+    o = 0
+    for f in picked:
+        ref_p, ref_d, _ = orc.detect(op, frames[f], w, h)
+        c = int(counts[f])
+        assert c == len(ref_p)
+        for k, name in enumerate(fields):
+            assert np.array_equal(pts[o:o + c, k], ref_p[name].astype(np.float32)), (f, name)
+        assert desc_l2(desc[o:o + c], ref_d).max() <= 1e-4
+        o += c
+
+
 def test_bench_exchange_proxy():
     """N = 1 with --exchange-proxy 8: the step re-timed with
     the HBM traffic an 8-rank all-gather lands on this GPU, (8-1) x slab
     bytes per step beside compute, in both gather modes."""
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--batch", "16", "--steps", "4",
-                        "--warmup", "1", "--no-cpu", "--no-exchange-probe", "--no-stream-peak", "--exchange-proxy", "8"],
+                        "--warmup", "1", "--full", "--no-cpu", "--no-exchange-probe", "--no-stream-peak",
+                        "--exchange-proxy", "8"],
                        capture_output=True, text=True, timeout=240, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

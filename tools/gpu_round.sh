@@ -14,7 +14,7 @@ if [ -z "$SKIP" ]; then
       > $O/${TAG}_pytest.log 2>&1 || { tail -60 $O/${TAG}_pytest.log; exit 1; }
   tail -3 $O/${TAG}_pytest.log
 fi
-timeout -k 10 300 python3 bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { tail -20 $O/${TAG}_bench.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { tail -20 $O/${TAG}_bench.err; exit 1; }
 cat $O/${TAG}_bench.json
 bash tools/profile_configs.sh ${TAG} || exit $?
 if [ -z "$SKIP" ]; then

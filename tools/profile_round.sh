@@ -20,7 +20,7 @@ mkdir -p gpurun_out
 OUT=gpurun_out
 SQ="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VALU"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -T -f csv -d $OUT/prof_${TAG}_kt -o run -- \
-    python3 bench.py --steps $STEPS --warmup 1 --no-cpu --no-stream-peak "$@" > $OUT/prof_${TAG}_kt.json 2> $OUT/prof_${TAG}_kt.err || exit $?
+    python3 bench.py --full --steps $STEPS --warmup 1 --no-cpu --no-stream-peak "$@" > $OUT/prof_${TAG}_kt.json 2> $OUT/prof_${TAG}_kt.err || exit $?
 timeout -s KILL 120 rocprofv3 --pmc $SQ -T -f csv -d $OUT/prof_${TAG}_sq -o run -- \
     python3 bench.py --steps 3 --warmup 1 --no-cpu --no-profile --no-stream-peak "$@" > $OUT/prof_${TAG}_sq.json 2> $OUT/prof_${TAG}_sq.err || exit $?
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -T -f csv -d $OUT/prof_${TAG}_fetch -o run -- \
