@@ -126,6 +126,7 @@ _sigs = {
     "surfhip_pack_slab_cap": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _sz]),
     "surfhip_match_scratch": (_sz, [_i, _i, _i]),
     "surfhip_match": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "surfhip_match_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "surfhip_ingest_create": (_i, [C.POINTER(_vp), _vp, _i]),
     "surfhip_ingest_destroy": (_i, [_vp]),
     "surfhip_ingest_acquire": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_sz)]),
@@ -533,6 +534,21 @@ def match_points(pts1_ptr: int, pts2_ptr: int, feat1_ptr: int, feat2_ptr: int, n
 
 def match_scratch_bytes(n1: int, n2: int, flags: int = 0) -> int:
     return int(_lib.surfhip_match_scratch(n1, n2, flags))
+
+
+MATCH_SAME_LAPLACE = 2      # match_batch only
+
+
+def match_batch(pts1_ptr: int, desc1_ptr: int, counts1_ptr: int, slots1: int, pts2_ptr: int, desc2_ptr: int,
+                counts2_ptr: int, slots2: int, npairs: int, nfeatures: int, flags: int = 0, stream=None) -> None:
+    """surfhip_match_batch: pair i = frame i of set 1 against frame i of set
+    2, on the detect_batch output layout ([npairs][slots] points and
+    descriptors, device counts), one launch, asynchronous on `stream`.
+    Consecutive frames of one batch: set 2 = set 1 advanced by one frame
+    (pts + 48 * slots, desc + 4 * slots * nfeatures, counts + 4 bytes) and
+    npairs = nframes - 1."""
+    check(_lib.surfhip_match_batch(pts1_ptr, desc1_ptr, counts1_ptr, slots1, pts2_ptr, desc2_ptr, counts2_ptr,
+                                   slots2, npairs, nfeatures, flags, stream), "surfhip_match_batch")
 
 
 # ---------------------------------------------------------------- frames

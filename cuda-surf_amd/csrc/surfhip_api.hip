@@ -1050,6 +1050,20 @@ int surfhip_match(surfhip_point* pts1, const surfhip_point* pts2, const float* f
     return SURFHIP_OK;
 }
 
+int surfhip_match_batch(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
+                        const surfhip_point* pts2, const float* f2, const int* counts2, int slots2, int npairs,
+                        int nf, int flags, void* stream)
+{
+    if (npairs < 0 || slots1 <= 0 || slots2 <= 0 || nf < 4 || nf > 1024 || (nf & 3) ||
+        (flags & ~(SURFHIP_MATCH_FULL_TAIL | SURFHIP_MATCH_SAME_LAPLACE)))
+        return SURFHIP_ERR_INVALID;
+    if (npairs == 0) return SURFHIP_OK;
+    if (!pts1 || !f1 || !counts1 || !pts2 || !f2 || !counts2) return SURFHIP_ERR_INVALID;
+    HIPCHK(launch_match_batch(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf, flags,
+                              (hipStream_t)stream));
+    return SURFHIP_OK;
+}
+
 /* ------------------------------------------------------------- ingest --
  * Pipelined host -> HBM -> result-slab ring.  The
  * reference feeds one frame per call through a blocking cudaMemcpy2D of a

@@ -200,6 +200,12 @@ hipError_t launch_double(const uint8_t* frames, int pitch, long long fstride, in
 size_t match_scratch_bytes(int n1, int n2, int flags);
 hipError_t launch_match(surfhip_point* pts1, const surfhip_point* pts2, const float* f1, const float* f2, int n1,
                         int n2, int nf, int flags, void* scratch, hipStream_t s);
+// Batched matching on the f32 MFMA: pair i = frame i of set 1 ([npairs][slots1]
+// points / descriptors, counts on the device) against frame i of set 2; no
+// scratch.  The point arrays may overlap (set 2 = set 1 advanced one frame).
+hipError_t launch_match_batch(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
+                              const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
+                              int npairs, int nf, int flags, hipStream_t s);
 hipError_t launch_pack(const surfhip_point* pts, const float* desc, const int* counts, const int* offsets,
                        int nframes, int max_pts, int nfeat, const int* status, size_t cap_bytes, uint8_t* slab,
                        hipStream_t s);

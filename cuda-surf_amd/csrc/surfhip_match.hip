@@ -21,9 +21,31 @@
 //     a tie: exactly the sequential scan's result); the row-0 lane then does
 //     the reference's row merge over lane shuffles and writes the five
 //     SurfPoint fields.
-// No dense-contraction unit is used: MFMA would re-associate the sums and
-// break bit-exact scores (and so argmax ties); at ~3k x 3k x 64 the FMA
-// chains cost tens of microseconds.
+// These two kernels run the chains on the VALU; at ~3k x 3k x 64 they cost
+// tens of microseconds per pair.
+//
+// Batched matching (surfhip_match_batch), pair i = frame i of set 1 against
+// frame i of set 2 in the surfhip_detect_batch layout, runs the same chains
+// on the matrix cores.  On gfx950 v_mfma_f32_32x32x2_f32 is bit-for-bit a
+// k-ordered fmaf chain (one rounding per product, no wider accumulation), so
+// chaining its k-steps s = 0, 1, .. into one accumulator that starts at 0,
+// with descriptor element 2 s on lanes 0-31 and 2 s + 1 on lanes 32-63, is
+// the reference's score, not a re-associated sum.
+//   * k_match_batch: grid (point tiles of set 1, pairs).  A wave owns 32
+//     set-1 points as the B operand (lane l: point l & 31, elements of
+//     parity l >> 5; resident in VGPRs for nf = 64 / 128), the pair's set-2
+//     tiles of 32 points are the A operand, staged once per block in LDS
+//     (even and odd elements of a row apart, so a lane reads its k-steps
+//     with 16-B loads; double-buffered, one barrier per tile).  The
+//     accumulator D[p2][p1] has p1 on the lane and tile positions
+//     8 q + 4 h + 0..3 (h = lane >> 5) in registers 4 q .. 4 q + 3: exactly
+//     thread row 2 q + h, in ascending order, so each lane keeps four row
+//     states and updates them from the accumulator registers.  After the
+//     last tile lanes l and l ^ 32 exchange (max, index) of their rows and
+//     the h = 0 lane does the row merge and writes the point.  The counts
+//     are read on the device: no scratch, no host sync, one launch.
+//   * k_match_batch_any: other descriptor lengths, both operands reloaded
+//     from memory at every k-step.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -194,6 +216,236 @@ __global__ __launch_bounds__(256) void k_match_merge(surfhip_point* __restrict__
     q.ambiguity = S / (M + 1e-6f);
 }
 
+// ---- batched matching on the f32 MFMA ----------------------------------
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kBatchWaves = 4;                      // one per SIMD; each owns 32 set-1 points
+constexpr int kBatchThreads = 64 * kBatchWaves;
+constexpr int kBatchPts = 32 * kBatchWaves;         // set-1 points per block
+
+__device__ __forceinline__ int clamp_count(int c, int slots) { return c < 0 ? 0 : (c > slots ? slots : c); }
+
+// One 32 x 32 score tile D[p2][p1] into the lane's four row states: register
+// 4 q + r holds tile position 8 q + 4 h + r, i.e. thread row 2 q + h, r
+// ascending.  lap2: the laplace of tile position (lane & 31), LAP only.
+template <bool LAP>
+__device__ __forceinline__ void scan_tile(const f32x16& acc, int t, int h, int nscan, int lap1, int lap2,
+                                          float (&mx)[4], float (&sc)[4], int (&ix)[4])
+{
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int j = 8 * q + 4 * h + r;
+            const int p2 = 32 * t + j;
+            bool ok = p2 < nscan;
+            if (LAP) {
+                const int l2 = __shfl(lap2, j);
+                ok = ok && l2 == lap1;
+            }
+            if (ok) scan_update(acc[4 * q + r], p2, mx[q], sc[q], ix[q]);
+        }
+    }
+}
+
+// Lanes l and l ^ 32 hold rows (0, 2, 4, 6) and (1, 3, 5, 7) of point p1;
+// the h = 0 lane merges them as k_match_merge does and writes the point.
+__device__ __forceinline__ void batch_finish(surfhip_point* pts1, const surfhip_point* pts2, int p1, int n1, int h,
+                                             const float (&mx)[4], const float (&sc)[4], const int (&ix)[4])
+{
+    float omx[4];
+    int oix[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        omx[q] = __shfl_xor(mx[q], 32);
+        oix[q] = __shfl_xor(ix[q], 32);
+    }
+    if (h != 0 || p1 >= n1) return;
+    float M = mx[0], S = sc[0];
+    int I = ix[0];
+#pragma unroll
+    for (int r = 1; r < 8; ++r) {
+        const float rm = (r & 1) ? omx[r >> 1] : mx[r >> 1];
+        const int ri = (r & 1) ? oix[r >> 1] : ix[r >> 1];
+        if (I != ri) {
+            if (rm > M) {
+                S = fmaxf(M, S);
+                M = rm;
+                I = ri;
+            } else if (rm > S) {
+                S = rm;
+            }
+        }
+    }
+    surfhip_point& q = pts1[p1];
+    q.score = M;
+    q.match = I;
+    q.match_x = I >= 0 ? pts2[I].x : 0.0f;
+    q.match_y = I >= 0 ? pts2[I].y : 0.0f;
+    q.ambiguity = S / (M + 1e-6f);
+}
+
+// pts1 / pts2 may overlap (consecutive frames of one batch): no __restrict__
+// on them; only the five match fields of pts1 are written and only x, y,
+// laplace of pts2 are read.
+template <int NF, bool LAP>
+__global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pts1, const float* __restrict__ f1,
+                                                               const int* __restrict__ counts1, int slots1,
+                                                               const surfhip_point* pts2,
+                                                               const float* __restrict__ f2,
+                                                               const int* __restrict__ counts2, int slots2,
+                                                               int full_tail)
+{
+    constexpr int RS = NF + 4;                              // LDS row: NF / 2 even, NF / 2 odd elements, pad
+    constexpr int C4 = NF / 4;                              // float4 per descriptor
+    constexpr int NV = 32 * C4 / kBatchThreads;             // float4 per thread per tile
+    static_assert(32 * C4 % kBatchThreads == 0, "tile staging");
+    __shared__ __attribute__((aligned(16))) float tile[2][32 * RS];
+
+    const int pair = blockIdx.y;
+    const int n1 = clamp_count(counts1[pair], slots1);
+    const int base = blockIdx.x * kBatchPts;
+    if (base >= n1) return;
+    const int n2 = clamp_count(counts2[pair], slots2);
+    const int nscan = full_tail ? n2 : 32 * (n2 / 32);
+    const int ntile = (nscan + 31) / 32;
+    pts1 += (size_t)pair * slots1;
+    pts2 += (size_t)pair * slots2;
+    f1 += (size_t)pair * slots1 * NF;
+    f2 += (size_t)pair * slots2 * NF;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int h = lane >> 5, c = lane & 31;
+    const int p1 = base + 32 * wave + c;
+    const bool wlive = base + 32 * wave < n1;               // a dead wave of a live block only stages tiles
+    const int q1 = p1 < n1 ? p1 : n1 - 1;
+
+    float b[NF / 2];                                        // b[s] = f1[p1][2 s + h]
+    {
+        const float4* bp = reinterpret_cast<const float4*>(f1 + (size_t)q1 * NF);
+#pragma unroll
+        for (int d = 0; d < C4; ++d) {
+            const float4 v = bp[d];
+            b[2 * d] = h ? v.y : v.x;
+            b[2 * d + 1] = h ? v.w : v.z;
+        }
+    }
+    const int lap1 = LAP ? pts1[q1].laplace : 0;
+
+    float mx[4], sc[4];
+    int ix[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        mx[q] = 0.0f;
+        sc[q] = 0.0f;
+        ix[q] = -1;
+    }
+
+    float4 v[NV];
+    int lap2 = 0, lapn = 0;
+    auto load_tile = [&](int t) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int idx = tid + kBatchThreads * i;
+            const int row = idx / C4, col = idx % C4;
+            const int p2 = min(32 * t + row, nscan - 1);    // rows past nscan: any valid row (never scanned)
+            v[i] = reinterpret_cast<const float4*>(f2 + (size_t)p2 * NF)[col];
+        }
+        if (LAP) lapn = pts2[min(32 * t + c, nscan - 1)].laplace;
+    };
+    auto store_tile = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int idx = tid + kBatchThreads * i;
+            const int row = idx / C4, col = idx % C4;
+            float* dst = &tile[buf][row * RS + 2 * col];
+            *reinterpret_cast<float2*>(dst) = make_float2(v[i].x, v[i].z);
+            *reinterpret_cast<float2*>(dst + NF / 2) = make_float2(v[i].y, v[i].w);
+        }
+    };
+
+    if (ntile > 0) {
+        load_tile(0);
+        store_tile(0);
+        lap2 = lapn;
+    }
+    __syncthreads();
+    for (int t = 0; t < ntile; ++t) {
+        const int cur = t & 1;
+        const bool more = t + 1 < ntile;
+        // unconditional (rows are clamped to valid ones; the last prefetch is
+        // unused): in a branch the loads' wait would end that branch, ahead
+        // of the MFMAs they are meant to run under
+        load_tile(t + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        if (wlive) {
+            const float4* ap = reinterpret_cast<const float4*>(&tile[cur][c * RS + h * (NF / 2)]);
+            f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+            for (int k = 0; k < NF / 8; ++k) {
+                const float4 a = ap[k];
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b[4 * k], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b[4 * k + 1], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b[4 * k + 2], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b[4 * k + 3], acc, 0, 0, 0);
+            }
+            scan_tile<LAP>(acc, t, h, nscan, lap1, lap2, mx, sc, ix);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (more) store_tile(cur ^ 1);
+        lap2 = lapn;
+        __syncthreads();
+    }
+    if (wlive) batch_finish(pts1, pts2, p1, n1, h, mx, sc, ix);
+}
+
+// Any descriptor length (a multiple of 4, <= 1024): both operands come from
+// memory at every k-step; no LDS, so a wave past n1 exits at once.
+template <bool LAP>
+__global__ __launch_bounds__(kBatchThreads) void k_match_batch_any(surfhip_point* pts1,
+                                                                   const float* __restrict__ f1,
+                                                                   const int* __restrict__ counts1, int slots1,
+                                                                   const surfhip_point* pts2,
+                                                                   const float* __restrict__ f2,
+                                                                   const int* __restrict__ counts2, int slots2,
+                                                                   int nf, int full_tail)
+{
+    const int pair = blockIdx.y;
+    const int n1 = clamp_count(counts1[pair], slots1);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int base = blockIdx.x * kBatchPts + 32 * wave;
+    if (base >= n1) return;
+    const int n2 = clamp_count(counts2[pair], slots2);
+    const int nscan = full_tail ? n2 : 32 * (n2 / 32);
+    const int ntile = (nscan + 31) / 32;
+    pts1 += (size_t)pair * slots1;
+    pts2 += (size_t)pair * slots2;
+    f1 += (size_t)pair * slots1 * nf;
+    f2 += (size_t)pair * slots2 * nf;
+    const int h = lane >> 5, c = lane & 31;
+    const int p1 = base + c;
+    const int q1 = p1 < n1 ? p1 : n1 - 1;
+    const float* r1 = f1 + (size_t)q1 * nf + h;
+    const int lap1 = LAP ? pts1[q1].laplace : 0;
+    float mx[4], sc[4];
+    int ix[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        mx[q] = 0.0f;
+        sc[q] = 0.0f;
+        ix[q] = -1;
+    }
+    for (int t = 0; t < ntile; ++t) {
+        const int q2 = min(32 * t + c, nscan - 1);
+        const float* r2 = f2 + (size_t)q2 * nf + h;
+        const int lap2 = LAP ? pts2[q2].laplace : 0;
+        f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (int d = 0; d < nf; d += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(r2[d], r1[d], acc, 0, 0, 0);
+        scan_tile<LAP>(acc, t, h, nscan, lap1, lap2, mx, sc, ix);
+    }
+    batch_finish(pts1, pts2, p1, n1, h, mx, sc, ix);
+}
+
 }  // namespace
 
 size_t match_scratch_bytes(int n1, int n2, int flags)
@@ -226,6 +478,47 @@ hipError_t launch_match(surfhip_point* pts1, const surfhip_point* pts2, const fl
     }
     k_match_merge<<<(8 * n1 + 255) / 256, 256, 0, s>>>(pts1, pts2, n1, nchunk, pmx, psc, pix);
     return hipGetLastError();
+}
+
+template <bool LAP>
+static void launch_match_batch_lap(dim3 grid, surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
+                                   const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
+                                   int nf, int full_tail, hipStream_t s)
+{
+    if (nf == 64)
+        k_match_batch<64, LAP><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2,
+                                                              full_tail);
+    else if (nf == 128)
+        k_match_batch<128, LAP><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2,
+                                                               full_tail);
+    else
+        k_match_batch_any<LAP><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2,
+                                                              nf, full_tail);
+}
+
+hipError_t launch_match_batch(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
+                              const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
+                              int npairs, int nf, int flags, hipStream_t s)
+{
+    const int full_tail = (flags & SURFHIP_MATCH_FULL_TAIL) ? 1 : 0;
+    constexpr int kMaxGridY = 65535;                        // one launch up to this many pairs
+    for (int p0 = 0; p0 < npairs; p0 += kMaxGridY) {
+        const int np = npairs - p0 < kMaxGridY ? npairs - p0 : kMaxGridY;
+        const dim3 grid((slots1 + kBatchPts - 1) / kBatchPts, np);
+        surfhip_point* a = pts1 + (size_t)p0 * slots1;
+        const surfhip_point* b = pts2 + (size_t)p0 * slots2;
+        const float* fa = f1 + (size_t)p0 * slots1 * nf;
+        const float* fb = f2 + (size_t)p0 * slots2 * nf;
+        if (flags & SURFHIP_MATCH_SAME_LAPLACE)
+            launch_match_batch_lap<true>(grid, a, fa, counts1 + p0, slots1, b, fb, counts2 + p0, slots2, nf,
+                                         full_tail, s);
+        else
+            launch_match_batch_lap<false>(grid, a, fa, counts1 + p0, slots1, b, fb, counts2 + p0, slots2, nf,
+                                          full_tail, s);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 }  // namespace surfhip

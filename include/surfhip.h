@@ -271,8 +271,8 @@ int surfhip_pack_slab_cap(surfhip_detector* det, const surfhip_point* d_points, 
  * match_x/match_y (that point's x, y; 0 for -1) and ambiguity
  * (second / (best + 1e-6)) -- the reference's per-thread-row top-2 and row
  * merge, bit-exact.  Descriptors: n x nfeatures f32 rows (nfeatures a
- * multiple of 4, <= 128).  flags: SURFHIP_MATCH_FULL_TAIL also scores the
- * last partial 32-point tile of set 2, which the reference drops
+ * multiple of 4, 4 .. 1024; 16-B aligned).  flags:
+ * SURFHIP_MATCH_FULL_TAIL also scores the last partial 32-point tile of set 2, which the reference drops
  * (surfd.cu:2569); 0 follows the reference.  Scratch (surfhip_match_scratch
  * bytes, device) is caller-provided (the call is then asynchronous), or
  * NULL: the library allocates it and the call returns after the stream has
@@ -282,6 +282,42 @@ size_t surfhip_match_scratch(int n1, int n2, int flags);
 int surfhip_match(surfhip_point* d_pts1, const surfhip_point* d_pts2, const float* d_feat1,
                   const float* d_feat2, int n1, int n2, int nfeatures, int flags,
                   void* d_scratch, void* stream);
+
+/* Batched matching (no reference counterpart: Surfor::match handles one
+ * pair): pair i = frame i of set 1 against frame i of set 2, i in
+ * [0, npairs), directly on the surfhip_detect_batch output layout with
+ * slots = its max_pts:
+ *   d_pts1    : [npairs][slots1] SurfPoint slots
+ *   d_desc1   : [npairs][slots1][nfeatures] f32 (16-B aligned)
+ *   d_counts1 : [npairs] int, read on the device; pair i uses
+ *               n1 = clamp(d_counts1[i], 0, slots1)
+ *   set 2     : the same shapes with slots2
+ * For each pair the result is exactly what surfhip_match writes for that
+ * pair: score, match (index within the set-2 frame, -1 when no score is
+ * positive), match_x, match_y and ambiguity of the first n1 points of the
+ * set-1 frame, bit-exact (the scores are the same k-ordered fp32 FMA chains,
+ * computed by the f32 matrix instruction).  Nothing else is written: the
+ * other fields of the points, slots at or past n1 and both descriptor
+ * arrays stay untouched.  One launch, no scratch, no host synchronisation;
+ * asynchronous on `stream`.
+ * Consecutive frames of one batch: pass set 2 as the same three buffers
+ * advanced by one frame (d_pts + slots, d_desc + slots * nfeatures,
+ * d_counts + 1) and npairs = nframes - 1.  The buffers then overlap; this is
+ * supported: only the five match fields of set-1 points are written and
+ * only x, y and laplace of set-2 points are read.
+ * flags: SURFHIP_MATCH_FULL_TAIL as above; SURFHIP_MATCH_SAME_LAPLACE (this
+ * call only) offers a set-2 point to a set-1 point's top-2 scan only when
+ * their `laplace` fields are equal (the classic SURF sign-of-Laplacian
+ * pruning); a skipped point keeps its position in its 32-point tile.
+ * nfeatures: a multiple of 4, 4 .. 1024.  SURFHIP_ERR_INVALID for
+ * npairs < 0, slots <= 0, a bad nfeatures, unknown flag bits, or a NULL
+ * pointer with npairs > 0; npairs == 0 returns SURFHIP_OK without touching
+ * the GPU.  For one or a few pairs surfhip_match, which splits set 2 over
+ * the chip, is the faster call. */
+#define SURFHIP_MATCH_SAME_LAPLACE 2
+int surfhip_match_batch(surfhip_point* d_pts1, const float* d_desc1, const int* d_counts1, int slots1,
+                        const surfhip_point* d_pts2, const float* d_desc2, const int* d_counts2, int slots2,
+                        int npairs, int nfeatures, int flags, void* stream);
 
 /* ------------------------------------------------------------- ingest --
  * Pipelined host-frame ingest.  Replaces the

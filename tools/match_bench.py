@@ -4,6 +4,15 @@ descriptors, caller-provided scratch, HIP events via torch on the null
 stream.  Prints one JSON line per case.
 
     python tools/match_bench.py [--n 3000] [--iters 50]
+
+--batch NPAIRS instead times NPAIRS pairs of n x n points (flags 0, nf 64
+then 128) two ways on the same data, alternating in one run: a loop of NPAIRS
+surfhip_match calls with caller scratch, and one surfhip_match_batch call.
+It checks that both write the same bits and prints, per nf, one JSON line
+with both times in ms (median and range over --reps), their ratio and the
+batch call's fp32 TFLOP/s.
+
+    python tools/match_bench.py --batch 255 [--n 3000] [--reps 7]
 """
 from __future__ import annotations
 
@@ -28,13 +37,67 @@ def load_surf():
     return mod
 
 
+def bench_batch(surf, torch, npairs, n, reps, inner):
+    for nf in (64, 128):
+        torch.manual_seed(nf)
+        ft = torch.randn((2, npairs, n, nf), device="cuda")
+        ft /= ft.norm(dim=3, keepdim=True)
+        pts = torch.zeros((2, npairs, n, 48), dtype=torch.uint8, device="cuda")
+        pts_b = torch.zeros((npairs, n, 48), dtype=torch.uint8, device="cuda")
+        counts = torch.full((2, npairs), n, dtype=torch.int32, device="cuda")
+        scratch = torch.empty(max(surf.match_scratch_bytes(n, n, 0), 4), dtype=torch.uint8, device="cuda")
+
+        def loop():
+            for i in range(npairs):
+                surf.match_points(pts[0, i].data_ptr(), pts[1, i].data_ptr(), ft[0, i].data_ptr(),
+                                  ft[1, i].data_ptr(), n, n, nf, 0, scratch.data_ptr())
+
+        def batch():
+            surf.match_batch(pts_b.data_ptr(), ft[0].data_ptr(), counts[0].data_ptr(), n, pts[1].data_ptr(),
+                             ft[1].data_ptr(), counts[1].data_ptr(), n, npairs, nf, 0)
+
+        loop()
+        batch()
+        torch.cuda.synchronize()
+        same = bool(torch.equal(pts[0], pts_b))
+        t_loop, t_batch = [], []
+        for _ in range(reps):                       # alternate the two in the same run
+            for fn, k, out in ((loop, 1, t_loop), (batch, inner, t_batch)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(k):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                out.append(e0.elapsed_time(e1) / k)
+        lm, bm = float(np.median(t_loop)), float(np.median(t_batch))
+        fma = npairs * n * (32 * (n // 32)) * nf
+        print(json.dumps({"case": f"match {npairs} pairs of {n}x{n} nf={nf} flags=0",
+                          "loop_ms": round(lm, 4), "loop_ms_range": [round(min(t_loop), 4), round(max(t_loop), 4)],
+                          "batch_ms": round(bm, 4),
+                          "batch_ms_range": [round(min(t_batch), 4), round(max(t_batch), 4)],
+                          "ratio": round(lm / bm, 3), "batch_fp32_tflops": round(2 * fma / bm / 1e9, 2),
+                          "loop_fp32_tflops": round(2 * fma / lm / 1e9, 2), "reps": reps,
+                          "bit_identical": same}), flush=True)
+        if not same:
+            raise SystemExit("surfhip_match_batch and the surfhip_match loop disagree")
+        del ft, pts, pts_b, scratch
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=3000)
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--batch", type=int, default=0, metavar="NPAIRS",
+                    help="time NPAIRS surfhip_match calls against one surfhip_match_batch call")
+    ap.add_argument("--reps", type=int, default=7, help="--batch: timed repeats of each side")
+    ap.add_argument("--inner", type=int, default=4, help="--batch: batch calls per timed window")
     args = ap.parse_args()
     import torch
     surf = load_surf()
+    if args.batch > 0:
+        bench_batch(surf, torch, args.batch, args.n, args.reps, args.inner)
+        return
     for nf in (64, 128):
         for flags in (0, 1):
             n = args.n
