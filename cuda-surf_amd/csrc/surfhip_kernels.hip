@@ -1093,7 +1093,8 @@ __device__ __forceinline__ int32_t trace_sign(const uint32_t* __restrict__ I, in
 // cube: the scan's record of the 19 responses around (s, r, c) (nullptr:
 // read them from the planes)
 // stash: leave getTrace to k_describe_u2 (trace_in_describe): laplace holds
-// its box centre x0 | y0 << 16 (int16 each) and ori the lobe `temp`, which
+// its box centre x0 | y0 << 16 (int16 each: trace_in_describe keeps frames of
+// 32768 integral rows or more off this path) and ori the lobe `temp`, which
 // the describe kernel replaces by the sign and 0
 __device__ bool nms_fit_point(const uint32_t* __restrict__ I, const OctView& V, const FrameParams& P,
                               const OctaveParams& q, int o, int s, int r, int c, const float4* cube,
@@ -3409,7 +3410,11 @@ bool describe_on_u2(const FrameParams& P, int nframes)
 bool trace_in_describe(const FrameParams& P, int nframes)
 {
     const char* e = getenv("SURFHIP_TRACE_DESC");
-    return (e ? atoi(e) != 0 : true) && describe_on_u2(P, nframes);
+    // the fit's stash holds the box centre as two int16 (nms_fit_point,
+    // decoded signed in k_describe_u2): from integral row / column 32768 on
+    // the sign stays in the fit (trace_sign), whatever the switch says
+    const bool fits16 = P.iH < 32768 && P.W + 1 < 32768;
+    return (e ? atoi(e) != 0 : true) && fits16 && describe_on_u2(P, nframes);
 }
 
 hipError_t launch_describe(const int32_t* ii, const FrameParams& P, surfhip_point* pts, int max_pts,

@@ -130,7 +130,17 @@ int surfhip_make_param(surfhip_param* out, int noctaves, float thresh, int doubl
  * cuHalfImage/cuCalcHessianMulti/cuFindMaximumWithInterp per octave
  * (surf.cpp:248-294, surfd.cu:2775, 2829, 3058) -> cuDescribe (surfd.cu:3251).
  *   d_frames : nframes u8 frames, row pitch `pitch` bytes (>= W, multiple of
- *              16), frame f at d_frames + f*frame_stride (16-B aligned)
+ *              16), frame f at d_frames + f*frame_stride (16-B aligned;
+ *              frame_stride >= pitch*H and a multiple of 16 when nframes >
+ *              1).  Pad bytes past column W and bytes between frames are
+ *              never used, whatever they hold.  Any size the detector was
+ *              created with is supported: widths to 8,191 columns (after
+ *              doubling) and any height whose octave-0 sample grid stays
+ *              below 16,384 rows (about 65,000 rows at sampling_step 4),
+ *              frames of 32,767 rows and more included -- for those the
+ *              laplace sign is taken in the fit, not in the describe kernel
+ *              (its stash holds 16-bit coordinates); SURFHIP_ERR_INVALID for
+ *              a layout outside this contract
  *   d_points : [nframes][max_pts] SurfPoint slots (device)
  *   d_desc   : [nframes][max_pts][nfeatures] f32 (device) or NULL (desc=false)
  *   d_counts : [nframes] int (device): keypoints kept per frame
