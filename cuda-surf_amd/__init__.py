@@ -127,6 +127,8 @@ _sigs = {
     "surfhip_match_scratch": (_sz, [_i, _i, _i]),
     "surfhip_match": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "surfhip_match_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "surfhip_homography_batch": (_i, [_vp, _vp, _i, _i, C.c_float, C.c_float, _i, C.c_uint32, _vp, _vp, _vp]),
+    "surfhip_homography_lds_capacity": (_i, []),
     "surfhip_ingest_create": (_i, [C.POINTER(_vp), _vp, _i]),
     "surfhip_ingest_destroy": (_i, [_vp]),
     "surfhip_ingest_acquire": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_sz)]),
@@ -549,6 +551,28 @@ def match_batch(pts1_ptr: int, desc1_ptr: int, counts1_ptr: int, slots1: int, pt
     npairs = nframes - 1."""
     check(_lib.surfhip_match_batch(pts1_ptr, desc1_ptr, counts1_ptr, slots1, pts2_ptr, desc2_ptr, counts2_ptr,
                                    slots2, npairs, nfeatures, flags, stream), "surfhip_match_batch")
+
+
+# ------------------------------------------------------------ homography
+
+HOMOG_OK, HOMOG_TOO_FEW, HOMOG_DEGENERATE = 0, 1, 2
+HOMOGRAPHY_DTYPE = np.dtype([("h", "<f4", (9,)), ("status", "<i4"), ("ncand", "<i4"), ("ninliers", "<i4"),
+                             ("rms", "<f4"), ("reserved", "<i4", (3,))])
+assert HOMOGRAPHY_DTYPE.itemsize == 64
+# candidates per pair the kernel keeps in LDS (larger pairs are exact too, only slower)
+HOMOGRAPHY_LDS_CAPACITY = int(_lib.surfhip_homography_lds_capacity())
+
+
+def homography_batch(pts1_ptr: int, counts1_ptr: int, slots1: int, npairs: int, out_ptr: int,
+                     inlier_ptr: int | None = None, max_ambiguity: float = 0.95, inlier_thresh: float = 3.0,
+                     nhyp: int = 256, seed: int = 0, stream=None) -> None:
+    """surfhip_homography_batch: one RANSAC homography (x, y) -> (match_x,
+    match_y) per pair from the match fields match_batch left in the set-1
+    points ([npairs][slots1], device counts), asynchronous on `stream`.
+    out_ptr: [npairs] HOMOGRAPHY_DTYPE records; inlier_ptr: [npairs][slots1]
+    bytes or None."""
+    check(_lib.surfhip_homography_batch(pts1_ptr, counts1_ptr, slots1, npairs, max_ambiguity, inlier_thresh, nhyp,
+                                        seed & 0xFFFFFFFF, out_ptr, inlier_ptr, stream), "surfhip_homography_batch")
 
 
 # ---------------------------------------------------------------- frames

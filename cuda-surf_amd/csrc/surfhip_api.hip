@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 
 #include "surfhip.h"
 #include "surfhip_internal.h"
@@ -1063,6 +1064,24 @@ int surfhip_match_batch(surfhip_point* pts1, const float* f1, const int* counts1
                               (hipStream_t)stream));
     return SURFHIP_OK;
 }
+
+static_assert(sizeof(surfhip_homography) == 64, "surfhip_homography is 64 bytes");
+
+int surfhip_homography_batch(const surfhip_point* pts1, const int* counts1, int slots1, int npairs,
+                             float max_ambiguity, float inlier_thresh, int nhyp, uint32_t seed,
+                             surfhip_homography* out, uint8_t* inlier, void* stream)
+{
+    if (npairs < 0 || slots1 <= 0 || nhyp < 1 || nhyp > 4096 || !std::isfinite(max_ambiguity) ||
+        !(max_ambiguity > 0.0f) || !std::isfinite(inlier_thresh) || !(inlier_thresh > 0.0f))
+        return SURFHIP_ERR_INVALID;
+    if (npairs == 0) return SURFHIP_OK;
+    if (!pts1 || !counts1 || !out) return SURFHIP_ERR_INVALID;
+    HIPCHK(launch_homography_batch(pts1, counts1, slots1, npairs, max_ambiguity, inlier_thresh, nhyp, seed, out,
+                                   inlier, (hipStream_t)stream));
+    return SURFHIP_OK;
+}
+
+int surfhip_homography_lds_capacity(void) { return kHomogCap; }
 
 /* ------------------------------------------------------------- ingest --
  * Pipelined host -> HBM -> result-slab ring.  The

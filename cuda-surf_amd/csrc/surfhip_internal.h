@@ -206,6 +206,13 @@ hipError_t launch_match(surfhip_point* pts1, const surfhip_point* pts2, const fl
 hipError_t launch_match_batch(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
                               const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
                               int npairs, int nf, int flags, hipStream_t s);
+// Batched RANSAC homographies (surfhip_homography.hip): one workgroup per
+// pair on the match fields of its set-1 points; kHomogCap candidates per
+// pair stay in LDS, more are re-read from the point array.
+constexpr int kHomogCap = 3072;
+hipError_t launch_homography_batch(const surfhip_point* pts, const int* counts, int slots, int npairs, float max_amb,
+                                   float thresh, int nhyp, uint32_t seed, surfhip_homography* out, uint8_t* inlier,
+                                   hipStream_t s);
 hipError_t launch_pack(const surfhip_point* pts, const float* desc, const int* counts, const int* offsets,
                        int nframes, int max_pts, int nfeat, const int* status, size_t cap_bytes, uint8_t* slab,
                        hipStream_t s);

@@ -329,6 +329,55 @@ int surfhip_match_batch(surfhip_point* d_pts1, const float* d_desc1, const int* 
                         const surfhip_point* d_pts2, const float* d_desc2, const int* d_counts2, int slots2,
                         int npairs, int nfeatures, int flags, void* stream);
 
+/* ---------------------------------------------------------- homography --
+ * Batched RANSAC homographies (no reference counterpart: main.cpp:250-262
+ * only draws the matches): one 3 x 3 matrix per frame pair from the match
+ * fields surfhip_match_batch left in the set-1 points, asynchronous on
+ * `stream`, one launch sequence, no scratch, no host synchronisation.
+ *   d_pts1    : [npairs][slots1] SurfPoint slots, as surfhip_match_batch
+ *               wrote them; only x, y, match, match_x, match_y and ambiguity
+ *               are read, nothing is written
+ *   d_counts1 : [npairs] int, read on the device, clamped to [0, slots1]
+ *   d_out     : [npairs] results
+ *   d_inlier  : [npairs][slots1] bytes or NULL: 1 for a final inlier, 0 for
+ *               every other slot (slots at or past the count included)
+ * A point below the count is a candidate when match >= 0 and ambiguity <=
+ * max_ambiguity; candidates keep the order of their indices.  nhyp (1 ..
+ * 4096) four-point hypotheses are drawn by a counter hash of (seed,
+ * hypothesis index, ncand) alone, so a pair gives the same bits
+ * wherever it sits in a batch and from run to run.  An inlier has a squared
+ * transfer error in image 2 below inlier_thresh^2 (strict, fp32; a point
+ * that projects to w <= 0 is an outlier).  The hypothesis with the most
+ * inliers (the lowest index on a tie) is refined by exactly two rounds of a
+ * Hartley-normalised least-squares DLT over the current inliers (fp64) and
+ * a recount; h, ninliers, rms and the mask belong to the last round.
+ * Fewer than 4 candidates: SURFHIP_HOMOG_TOO_FEW; no usable hypothesis or
+ * refit (collinear or coincident points, |h33| vanishing against ||H||):
+ * SURFHIP_HOMOG_DEGENERATE; both with h = identity, ninliers = 0, rms = 0
+ * and a zero mask row.  The output never holds a NaN or an infinity.
+ * SURFHIP_ERR_INVALID for npairs < 0, slots1 <= 0, nhyp outside 1 .. 4096,
+ * an inlier_thresh or max_ambiguity that is not finite and positive, or a
+ * NULL d_pts1 / d_counts1 / d_out with npairs > 0; npairs == 0 returns
+ * SURFHIP_OK without touching the GPU. */
+#define SURFHIP_HOMOG_OK          0
+#define SURFHIP_HOMOG_TOO_FEW     1   /* fewer than 4 candidates */
+#define SURFHIP_HOMOG_DEGENERATE  2   /* no usable hypothesis / refit */
+typedef struct surfhip_homography {   /* 64 B */
+    float h[9];        /* row-major, maps (x, y) -> (match_x, match_y); h[8] == 1.0f when status == OK */
+    int   status;
+    int   ncand;       /* points that passed the filter */
+    int   ninliers;    /* of the final model */
+    float rms;         /* rms transfer error of the final inliers, px */
+    int   reserved[3]; /* written as 0 */
+} surfhip_homography;
+int surfhip_homography_batch(const surfhip_point* d_pts1, const int* d_counts1, int slots1,
+                             int npairs, float max_ambiguity, float inlier_thresh,
+                             int nhyp, uint32_t seed, surfhip_homography* d_out,
+                             uint8_t* d_inlier, void* stream);
+/* Candidates per pair the kernel keeps in LDS; pairs with more are still
+ * exact, the rest is re-read from the point array. */
+int surfhip_homography_lds_capacity(void);
+
 /* ------------------------------------------------------------- ingest --
  * Pipelined host-frame ingest.  Replaces the
  * per-frame blocking cudaMemcpy2D of a pageable frame (main.cpp:212-226) and
