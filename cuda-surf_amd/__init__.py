@@ -116,6 +116,7 @@ _sigs = {
     "surfhip_detector_hessian_times": (_i, [_vp, C.POINTER(C.c_float), _i, C.POINTER(_i)]),
     "surfhip_detector_workspace": (_i, [_vp, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_vp), C.POINTER(_sz)]),
     "surfhip_detector_geometry": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_longlong), C.POINTER(_i)]),
+    "surfhip_detector_rowsums": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "surfhip_run_integral": (_i, [_vp, _vp, _i, _i, _sz]),
     "surfhip_run_hessian": (_i, [_vp, _i]),
     "surfhip_hessian_bytes_per_frame": (C.c_longlong, [_vp]),
@@ -392,6 +393,15 @@ class Detector:
         osize = (C.c_int * 8)()
         check(_lib.surfhip_detector_geometry(self.h, iwhp, swhp, ooff, osize), "geometry")
         return (tuple(iwhp), [tuple(swhp[3 * o:3 * o + 3]) for o in range(8)], list(ooff), list(osize))
+
+    def rowsums(self):
+        """(device pointer, strips, rows per strip, source) of the row sums the
+        integral-writing Hessian kernel uses (surfhip_detector_rowsums);
+        source 0: none, 1: k_ii_rowseg, 2: k_hess_p0."""
+        p, ns, rows, src = C.c_void_p(), _i(), _i(), _i()
+        check(_lib.surfhip_detector_rowsums(self.h, C.byref(p), C.byref(ns), C.byref(rows), C.byref(src)),
+              "rowsums")
+        return p.value, ns.value, rows.value, src.value
 
     def hessian_bytes_per_frame(self) -> int:
         return int(_lib.surfhip_hessian_bytes_per_frame(self.h))

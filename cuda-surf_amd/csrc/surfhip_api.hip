@@ -75,6 +75,9 @@ struct surfhip_detector {
     // plan.iiw: k_ii_rowseg's row sums of the batch (or of the next batch,
     // prefetched) that k_hess_w adds to its strip integrals
     uint32_t* rowseg = nullptr;
+    // plan.rsum: k_hess_p0's per-strip row sums of the batch, which
+    // k_rowsum_p0 adds up into rowseg (no k_ii_rowseg pass, no prefetch)
+    uint32_t* psum = nullptr;
     surfhip_point* cand = nullptr;
     uint32_t* keys = nullptr;
     uint64_t* gscratch = nullptr;
@@ -425,7 +428,7 @@ static int derive(surfhip_detector* d)
 
 static void free_all(surfhip_detector* d)
 {
-    void* ptrs[] = {d->d_oct, d->iib[0], d->iib[1], d->resp, d->colsum, d->rowseg, d->cand, d->keys, d->gscratch, d->cand_count,
+    void* ptrs[] = {d->d_oct, d->iib[0], d->iib[1], d->resp, d->colsum, d->rowseg, d->psum, d->cand, d->keys, d->gscratch, d->cand_count,
                     d->scan_key, d->scan_src, d->scan_cube, d->item_count, d->item_off,
                     d->offsets, d->order, d->work, d->status, d->pts1, d->desc1, d->count1, d->dbl};
     for (void* p : ptrs)
@@ -500,6 +503,7 @@ int surfhip_detector_create(surfhip_detector** out, const surfhip_param* param, 
         // the stage also writes the integral image (read: the u8 frame)
         d->hess_bytes += (long long)d->W * d->H;
         ALLOC(d->rowseg, B * d->plan.rs_nstrips * d->plan.rs_rows * sizeof(uint32_t));
+        if (d->plan.rsum) ALLOC(d->psum, B * d->plan.q0_strips * d->plan.rs_rows * sizeof(uint32_t));
     }
     ALLOC(d->d_oct, sizeof(OctaveParams) * kMaxOct);
     ALLOC(d->iib[0], B * d->P.ii_stride * sizeof(int32_t));
@@ -633,7 +637,7 @@ int surfhip_run_hessian(surfhip_detector* d, int nframes)
     // the u8 Hessian kernels read the frames of the last run_integral
     if (!d->last_frames && plan_reads_frames(d->plan)) return SURFHIP_ERR_INVALID;
     HIPCHK(launch_hessian(d->last_frames, d->last_pitch, d->last_fstride, d->ii, d->resp, nframes, d->P, d->d_oct,
-                          d->oct, d->plan, d->stream, 3, d->rowseg, d->ii));
+                          d->oct, d->plan, d->stream, 3, d->rowseg, d->ii, d->psum));
     return SURFHIP_OK;
 }
 
@@ -689,7 +693,7 @@ int surfhip_detect_batch_next(surfhip_detector* d, const uint8_t* frames, int nf
         else HIPCHK(launch_integral(frames, pitch, (long long)stride, nframes, d->P, d->colsum, d->ii, s));
         HIPCHK(hipEventRecord(d->ev[1], s));
         HIPCHK(launch_hessian(frames, pitch, (long long)stride, d->ii, d->resp, nframes, d->P, d->d_oct, d->oct,
-                              d->plan, s, 3, d->rowseg, d->ii));
+                              d->plan, s, 3, d->rowseg, d->ii, d->psum));
         HIPCHK(hipEventRecord(d->ev[2], s));
     } else {
         // In-step Hessian timing brackets the WHOLE stage: from the fork (on
@@ -716,10 +720,10 @@ int surfhip_detect_batch_next(surfhip_detector* d, const uint8_t* frames, int nf
                 HIPCHK(launch_rowseg(frames, pitch, (long long)stride, nframes, d->P, d->plan, d->rowseg, s));
             if (th) HIPCHK(hipEventRecord(d->hev[d->hev_n][0], s));
             HIPCHK(launch_hessian(frames, pitch, (long long)stride, d->ii, d->resp, nframes, d->P, d->d_oct, d->oct,
-                                  d->plan, s, 4, d->rowseg, d->ii));
+                                  d->plan, s, 4, d->rowseg, d->ii, d->psum));
             if (have && !p0w) HIPCHK(hipStreamWaitEvent(s, d->join, 0));
             HIPCHK(launch_hessian(frames, pitch, (long long)stride, d->ii, d->resp, nframes, d->P, d->d_oct, d->oct,
-                                  d->plan, s, 8 | 2, d->rowseg, d->ii));
+                                  d->plan, s, 8 | 2, d->rowseg, d->ii, d->psum));
             if (th) {
                 HIPCHK(hipEventRecord(d->hev[d->hev_n][1], s));
                 d->hev_side[d->hev_n++] = false;
@@ -797,27 +801,36 @@ int surfhip_detect_batch_next(surfhip_detector* d, const uint8_t* frames, int nf
         return hipSuccess;
     };
     // (iiw: the prefetch is the row-sum pass, default beside describe, whose
-    // waves leave room for its 16-VGPR waves; SURFHIP_PREFETCH=nms / describe)
+    // waves leave room for its 16-VGPR waves; SURFHIP_PREFETCH=nms / describe
+    // / tail.  tail (iiw only, elsewhere nms): forked right after k_nms_scan,
+    // beside the small grids of the scan's prefix, the fit, the sort and the
+    // worklist, which leave most of the chip empty.  plan.rsum: k_hess_p0
+    // makes the row sums of its own batch, nothing to prefetch)
     static const int pref_env = [] {
         const char* e = getenv("SURFHIP_PREFETCH");
-        return !e ? -1 : !strcmp(e, "describe") ? 0 : 1;
+        return !e ? -1 : !strcmp(e, "describe") ? 0 : !strcmp(e, "tail") ? 2 : 1;
     }();
-    const bool pref_nms = pref_env < 0 ? !iiw : pref_env == 1;
-    if (pipe && pref_nms) HIPCHK(prefetch_next());
+    const bool pref_on = pipe && !(iiw && d->plan.rsum);
+    const bool pref_tail = iiw && pref_env == 2;
+    const bool pref_nms = !pref_tail && (pref_env < 0 ? !iiw : pref_env >= 1);
+    if (pref_on && pref_nms) HIPCHK(prefetch_next());
+    std::function<hipError_t()> after_scan;
+    if (pref_on && pref_tail) after_scan = prefetch_next;
     // getTrace in k_describe_u2 (its integral rows are in L2 there) rather
     // than in the fit (16 scattered integral loads per survivor from HBM)
     const bool trace_desc = desc && trace_in_describe(d->P, nframes);
     HIPCHK(launch_nms(d->ii, d->resp, nframes, d->P, d->d_oct, d->plan, d->scan_key, d->scan_src, d->scan_cube,
-                      d->item_count, d->item_off, d->cand, d->keys, d->cand_count, d->cap, d->status, s, trace_desc));
+                      d->item_count, d->item_off, d->cand, d->keys, d->cand_count, d->cap, d->status, s, trace_desc,
+                      after_scan ? &after_scan : nullptr));
     if (prof) HIPCHK(hipEventRecord(d->ev[3], s));
     HIPCHK(launch_sort(d->cand, d->keys, d->gscratch, d->cand_count, d->item_off, d->plan.nms_start[kMaxOct] * 4,
                        d->cap, nframes, points, d->max_pts, counts, d->offsets, d->order, d->status, s));
     if (prof) HIPCHK(hipEventRecord(d->ev[4], s));
-    if (pipe && !pref_nms) HIPCHK(prefetch_next());
+    if (pref_on && !pref_nms && !pref_tail) HIPCHK(prefetch_next());
     if (d->desc_ev) HIPCHK(hipEventRecord(d->desc_ev, s));
     if (desc)
         HIPCHK(launch_describe(d->ii, d->P, points, d->max_pts, counts, d->offsets, d->order, d->work, nframes, desc,
-                               d->status + 64, s, pipe && !pref_nms && !iiw, d->cus, trace_desc));
+                               d->status + 64, s, pref_on && !pref_nms && !iiw, d->cus, trace_desc));
     if (prof) HIPCHK(hipEventRecord(d->ev[5], s));
     d->last_nframes = nframes;
     d->last_frames = frames;
@@ -961,6 +974,17 @@ int surfhip_detector_workspace(surfhip_detector* d, int32_t** ii, size_t* ii_str
     if (ii_stride) *ii_stride = (size_t)d->P.ii_stride;
     if (resp) *resp = d->resp;
     if (resp_stride) *resp_stride = (size_t)d->P.resp_stride;
+    return SURFHIP_OK;
+}
+
+int surfhip_detector_rowsums(surfhip_detector* d, uint32_t** rowseg, int* nstrips, int* rows, int* source)
+{
+    if (!d) return SURFHIP_ERR_INVALID;
+    const bool on = d->plan.iiw && d->plan.rs_nstrips >= 2;
+    if (rowseg) *rowseg = on ? d->rowseg : nullptr;
+    if (nstrips) *nstrips = on ? d->plan.rs_nstrips : 0;
+    if (rows) *rows = on ? d->plan.rs_rows : 0;
+    if (source) *source = !on ? 0 : d->plan.rsum ? 2 : 1;
     return SURFHIP_OK;
 }
 

@@ -37,6 +37,11 @@ constexpr int PD = SURF_P0_PD;
 constexpr int PD = 6;                     // producer: steps of u8 rows loaded ahead
 #endif
 static_assert(q0::P % PD == 0, "prefetch slot static within an epoch");
+// (RS) the integral writer's strips whose row sums the producer prepares:
+// k_hess_w's, halo column X_k = XST k - XHALO (hw::ST, hw::H; checked where
+// both are in scope)
+constexpr int XST = 480, XHALO = 144;
+static_assert(XST % 4 == 0 && XHALO % 4 == 0, "every X on a lane boundary (4 columns per lane)");
 }  // namespace p0
 #ifndef SURF_P0_PLANE_NT
 #define SURF_P0_PLANE_NT 1         // octave-0 plane stores non-temporal (0: default policy, A/B)
@@ -65,12 +70,25 @@ __device__ __forceinline__ void p0_barrier()
 // (the last strip: up to column W); BND: this strip's lane holding W masks
 // its pad columns past W to 0.  Rows of steps before the frame (k < 0) get an
 // offset past the store resource, rows past H fall outside it.
-template <int B, bool IIW, bool BND>
+// RS (plan.rsum, with k_hess_w writing the integral): the producer also
+// leaves k_hess_w's row sums half done, in place of k_ii_rowseg's pass over
+// the frames.  The ring holds a whole epoch of local-integral rows (NB = P),
+// so once per epoch lane j reads the rows around pixel row j at three columns
+// from LDS: the strip's first own column (lane 4's), the column after its
+// last (lane 36's) and, in the strip that holds a k_hess_w strip's halo
+// column X, that column (lane lx's; lx = 4: no X here, 0).  Differences of
+// consecutive rows are the pixel row's sums left of those columns; the
+// strip's own 128 columns and its columns left of X go as own | left << 16
+// into rsl (64 dwords of LDS, lane = row), which the last consumer wave
+// stores after the barrier (36 rows, one dword store per epoch).  Nothing is
+// added to the steps.  k_rowsum_p0 adds the strips up.
+template <int B, bool IIW, bool BND, bool RS>
 __device__ __forceinline__ void p0_producer(const uint8_t* __restrict__ frames, int pitch, long long fstride,
                                             const FrameParams& P, int f, int IX0, int niter, uint32_t* Tb,
                                             uint32_t* Tdb, const uint32_t* sg, int32_t* iib, bool last,
-                                            int rs_rows)
+                                            int rs_rows, uint32_t* rsl, int lx)
 {
+    static_assert(!(IIW && RS), "the row sums are prepared for k_hess_w's integral, not for this kernel's own");
     constexpr int NB = 2 * B;                              // ring slots
     static_assert(q0::P % NB == 0, "slot index static within an epoch; Delta read before rewritten");
     static_assert(2 * q0::P <= 64, "an epoch's row sums in one wave load");
@@ -106,6 +124,8 @@ __device__ __forceinline__ void p0_producer(const uint8_t* __restrict__ frames, 
         sv_next = __builtin_amdgcn_raw_buffer_load_b32(SR, (uint32_t)(-16 + lane) * 4u, 0, 0);
     }
     (void)vst; (void)pm1; (void)pm2; (void)pm3; (void)sv_cur; (void)ip4; (void)last;
+    static_assert(!RS || NB == q0::P, "an epoch's steps all in the ring when its row sums are taken");
+    (void)lx; (void)rsl;
     // no row test (k_hess_w's producer): rows outside the frame fall past the
     // buffer, or, for lanes left of the frame (c0 a multiple of 4), into
     // bytes cmask clears
@@ -215,6 +235,39 @@ __device__ __forceinline__ void p0_producer(const uint8_t* __restrict__ frames, 
                 s1 = (uint32_t)__builtin_amdgcn_readlane((int)sv_cur, 2 * K + 1);
             }
             scan_write(r0, r1, Tb + (K % NB) * (4 * q0::NJ), so, s0, s1);
+            if constexpr (RS && K == q0::P - 1) {
+                // the epoch's 18 steps are all in the ring (NB = P; the next
+                // step rewrites slot 0 only after this step's barrier): lane
+                // j < 36 takes pixel row 2 kb + j as L at row j + 1 minus L at
+                // row j.  Column entry (lane L, first column) is float2 2 L of
+                // plane 0: (L at row 2 k, L at row 2 k + 1) in slot k, L = the
+                // epoch's rows above summed over the columns left of it.
+                // Exact integers below 2^24.
+                // As floats: L at row i of the epoch, column entry e, is
+                // float (i / 2) 4 NJ + 2 e + (i & 1); row 36 is Ls0 (blended
+                // in with bit masks: a select on a loaded value would become
+                // a branch, and the loop's row loads would no longer be
+                // scheduled ahead across it).
+                typedef const float __attribute__((address_space(3))) lds_f;
+                const int r0i = lane < 2 * q0::P ? lane : 2 * q0::P - 1, r1i = r0i + 1;
+                const bool fin = r1i == 2 * q0::P;
+                const int r1c = fin ? r0i : r1i;
+                lds_f* F0 = (lds_f*)Tb + (r0i >> 1) * (4 * q0::NJ) + (r0i & 1);
+                lds_f* F1 = (lds_f*)Tb + (r1c >> 1) * (4 * q0::NJ) + (r1c & 1);
+                const uint32_t fm = fin ? ~0u : 0u;
+                auto blend = [&](float v, uint32_t e) {
+                    return __uint_as_float((__float_as_uint(v) & ~fm) | (__float_as_uint((float)e) & fm));
+                };
+                const float la = F0[2 * 8], lb = F0[2 * 72], lxv = F0[4 * lx];
+                const float ha = blend(F1[2 * 8], (uint32_t)__builtin_amdgcn_readlane((int)Ls0, 4));
+                const float hb = blend(F1[2 * 72], (uint32_t)__builtin_amdgcn_readlane((int)Ls0, 36));
+                const float hx = blend(F1[4 * lx], (uint32_t)__builtin_amdgcn_readlane((int)Ls0, lx));
+                const float da = ha - la, db = hb - lb, dx = hx - lxv;
+                // (to LDS: a store here would sit among the row loads in
+                // flight, which the compiler then waits for one by one)
+                typedef uint32_t __attribute__((address_space(3))) lds_u;
+                ((lds_u*)rsl)[lane] = (uint32_t)(db - da) | ((uint32_t)(dx - da) << 16);
+            }
 #else
             (void)k;
 #endif
@@ -228,9 +281,14 @@ __device__ __forceinline__ void p0_producer(const uint8_t* __restrict__ frames, 
 // --------------------------------------------------------------- consumers
 // Scales [S0, S1) of octave 0 (lobe 2s + 3) on one wave: k_hess_q0's step
 // for those scales (one read of each column entry they share).
-template <int B, int S0, int S1, int NT>
+// RSW: this wave also stores the row sums the producer left in rsl at the end
+// of its epoch, one barrier earlier (p0_producer), into rsb: the slab of
+// this frame and strip, row 2 (18 it - 8) + lane; rows outside [0, H) fall
+// outside the resource (a dword store: no store-data hazard).
+template <int B, int S0, int S1, int NT, bool RSW>
 __device__ __forceinline__ void p0_consumer(float* __restrict__ resp, const FrameParams& P, const OctaveParams& q,
-                                            int f, int IX0, int niter, const uint32_t* Tb, const uint32_t* Tdb)
+                                            int f, int IX0, int niter, const uint32_t* Tb, const uint32_t* Tdb,
+                                            const uint32_t* rsl, uint32_t* rsb)
 {
     constexpr int NB = 2 * B;
     constexpr int NSC = S1 - S0;
@@ -271,6 +329,8 @@ __device__ __forceinline__ void p0_consumer(float* __restrict__ resp, const Fram
 #define AXX(i, o) pxx[(i) >> 1][md((o) + q0::fin(S0 + (i)))][(i) & 1]
 #define AYY(i, o) pyy[(i) >> 1][md((o) + q0::fin(S0 + (i)))][(i) & 1]
 #define AXY(i, o) pxy[(i) >> 1][md((o) + q0::fin(S0 + (i)))][(i) & 1]
+    const rsrc_t QR = make_rsrc(rsb, RSW ? (long long)P.H * 4 : 0);
+    (void)QR; (void)rsl;
     p0_barrier();                       // the producer's first interval
 #ifdef SURF_DIAG_P0_NOCONS
     for (int t = 0; t < niter * (q0::P / B); t++) p0_barrier();
@@ -316,6 +376,14 @@ __device__ __forceinline__ void p0_consumer(float* __restrict__ resp, const Fram
                     });
                 });
 #undef DV
+            }
+            if constexpr (RSW && K == B) {
+                // the producer's epoch `it` ended at the barrier before this step
+                typedef const volatile uint32_t __attribute__((address_space(3))) lds_u;
+                const uint32_t rv = ((lds_u*)rsl)[lane];
+                const int row = 2 * (it * q0::P - 8) + lane;
+                const uint32_t ro = (lane < 2 * q0::P && row >= 0) ? (uint32_t)row * 4u : 0x40000000u;
+                __builtin_amdgcn_raw_buffer_store_b32(rv, QR, ro, 0, 0);
             }
             // the step's row pair at column x0 + dc: slot K % NB, plane dc & 1
             lds_v2f* Ts = Tl + (K % NB) * (2 * q0::NJ);
@@ -406,11 +474,14 @@ __host__ __device__ constexpr int p0_hi(int G, int w) { return w == G ? 5 : p0_l
 // x + 8, ..., a frame's strips together).  G: consumer waves (scale groups).
 // IIW: the producer also writes the integral image into iiw (rowseg: the
 // k_ii_rowseg<128, 16> sums of the same frames, rs_rows per strip slab).
-template <int B, int G, int NT, bool IIW>
+// RS: the producer also writes its strips' row sums into rsum (nframes x
+// nstrips slabs of rs_rows dwords: own | left << 16 per pixel row) for the xn
+// strips of k_hess_w (k_rowsum_p0 turns them into k_hess_w's row sums).
+template <int B, int G, int NT, bool IIW, bool RS = false>
 __global__ __launch_bounds__(64 * (1 + G)) __attribute__((amdgpu_waves_per_eu(G == 5 ? 5 : G == 4 ? 4 : G == 1 ? 2 : G == 2 ? 3 : 4))) void
 k_hess_p0(const uint8_t* __restrict__ frames, int pitch, long long fstride, float* __restrict__ resp, FrameParams P,
           OctaveParams q, int nstrips, int nframes, const uint32_t* __restrict__ rowseg, int32_t* __restrict__ iiw,
-          int rs_rows)
+          int rs_rows, uint32_t* __restrict__ rsum, int xn)
 {
     constexpr int NB = 2 * B;
     __shared__ __attribute__((aligned(16))) uint32_t T[NB][4 * q0::NJ];   // [slot][plane][NJ] float2
@@ -422,6 +493,12 @@ k_hess_p0(const uint8_t* __restrict__ frames, int pitch, long long fstride, floa
     if (threadIdx.x == 0 && nframes < 0) xlds[blockIdx.x & 15] = 1u;
     asm volatile("" ::"v"(xlds[threadIdx.x & 15]));
 #endif
+    // (RS) an epoch's row sums on their way from the producer to the wave that stores them
+    uint32_t* rsl = nullptr;
+    if constexpr (RS) {
+        __shared__ uint32_t RSL[64];
+        rsl = RSL;
+    }
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int xcd = blockIdx.x & 7, kb = blockIdx.x >> 3;
     const int f = (kb / nstrips) * 8 + xcd, strip = kb - (kb / nstrips) * nstrips;
@@ -435,19 +512,31 @@ k_hess_p0(const uint8_t* __restrict__ frames, int pitch, long long fstride, floa
             int32_t* iib = iiw + (size_t)f * P.ii_stride;
             // the strip whose lane holding column W has pad columns after it
             if (last && (P.W & 3) != 3)
-                p0_producer<B, true, true>(frames, pitch, fstride, P, f, IX0, niter, &T[0][0], TD, sg, iib, last,
-                                           rs_rows);
+                p0_producer<B, true, true, false>(frames, pitch, fstride, P, f, IX0, niter, &T[0][0], TD, sg, iib,
+                                                  last, rs_rows, nullptr, 4);
             else
-                p0_producer<B, true, false>(frames, pitch, fstride, P, f, IX0, niter, &T[0][0], TD, sg, iib, last,
-                                            rs_rows);
+                p0_producer<B, true, false, false>(frames, pitch, fstride, P, f, IX0, niter, &T[0][0], TD, sg, iib,
+                                                   last, rs_rows, nullptr, 4);
+        } else if constexpr (RS) {
+            // the k_hess_w strip (1 .. xn - 1) whose halo column X lies in
+            // this strip's columns [128 strip, + 128), if any: the lane whose
+            // first column is X (lane 4's is column 128 strip)
+            const int k = (128 * strip + p0::XHALO + p0::XST - 1) / p0::XST;
+            const int xo = p0::XST * k - p0::XHALO - 128 * strip;
+            const int lx = (k >= 1 && k < xn && xo < 128) ? 4 + (xo >> 2) : 4;
+            p0_producer<B, false, false, true>(frames, pitch, fstride, P, f, IX0, niter, &T[0][0], TD, nullptr,
+                                               nullptr, false, 0, rsl, lx);
         } else {
-            p0_producer<B, false, false>(frames, pitch, fstride, P, f, IX0, niter, &T[0][0], TD, nullptr, nullptr,
-                                         false, 0);
+            p0_producer<B, false, false, false>(frames, pitch, fstride, P, f, IX0, niter, &T[0][0], TD, nullptr,
+                                                nullptr, false, 0, nullptr, 4);
         }
         return;
     }
     static_for<G>([&](auto gc) {
         constexpr int wc = decltype(gc)::value + 1;
-        if (w == wc) p0_consumer<B, p0_lo(G, wc), p0_hi(G, wc), NT>(resp, P, q, f, IX0, niter, &T[0][0], TD);
+        if (w == wc)
+            p0_consumer<B, p0_lo(G, wc), p0_hi(G, wc), NT, RS && wc == G>(
+                resp, P, q, f, IX0, niter, &T[0][0], TD, rsl,
+                RS ? rsum + ((size_t)f * nstrips + strip) * rs_rows : nullptr);
     });
 }

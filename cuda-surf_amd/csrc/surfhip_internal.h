@@ -12,6 +12,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <functional>
 #include <string>
 
 #include "surfhip.h"
@@ -130,6 +131,10 @@ struct LaunchPlan {
     int iiw;
     int rs_rows;                    // rows per rowseg slab (4 x hw_nblk, zero past H)
     int rs_nstrips;                 // rowseg slabs per frame: the writer's strips
+    // iiw 1: k_hess_w's row sums come from k_hess_p0's producers (per
+    // 128-column strip, added up by k_rowsum_p0 between the two launches)
+    // instead of k_ii_rowseg's pass over the frames
+    int rsum;
 };
 // the plan has kernels that read the u8 frames (not only the integral image)
 inline bool plan_reads_frames(const LaunchPlan& p) { return p.q0 || p.q1 || p.hw_n > 0; }
@@ -150,22 +155,28 @@ std::string hessian_plan_text(const LaunchPlan& plan, const FrameParams& P);
 // only the k_hess_w launch of part 1.  ii_out + rowseg (plan.iiw):
 // k_hess_w (iiw 1) or k_hess_p0 (iiw 2) writes the frames' integral image
 // into ii_out (rowseg: the k_ii_rowseg sums of the same frames); nullptr:
-// neither does.
+// neither does.  psum (plan.rsum): nframes x q0_strips x rs_rows uint32 of
+// scratch; the octave-0 part then fills rowseg itself (k_hess_p0's strip
+// sums, k_rowsum_p0) and launch_rowseg does nothing.
 hipError_t launch_hessian(const uint8_t* frames, int pitch, long long fstride, const int32_t* ii, float* resp,
                           int nframes, const FrameParams& P, const OctaveParams* d_oct, const OctaveParams* h_oct,
-                          const LaunchPlan& plan, hipStream_t s, int parts = 3, const uint32_t* rowseg = nullptr,
-                          int32_t* ii_out = nullptr);
+                          const LaunchPlan& plan, hipStream_t s, int parts = 3, uint32_t* rowseg = nullptr,
+                          int32_t* ii_out = nullptr, uint32_t* psum = nullptr);
 // plan.iiw: the row sums the writer's strips add to their integral (rowseg:
 // nframes x rs_nstrips x rs_rows uint32; slab 0 and rows >= H stay zero)
+// (plan.rsum: no launch)
 hipError_t launch_rowseg(const uint8_t* frames, int pitch, long long fstride, int nframes, const FrameParams& P,
                          const LaunchPlan& plan, uint32_t* rowseg, hipStream_t s);
 // NMS scan items: one wave's 64 block columns x kScanRows / 4 block rows;
 // each item owns kItemCap survivor slots (no atomics in the scan).
 // (also zeroes cand_count[0, nframes) and *status, the per-batch counters)
+// after_scan: called once k_nms_scan is queued, before the scan's prefix and
+// the fit (the caller forks a side stream there)
 hipError_t launch_nms(const int32_t* ii, const float* resp, int nframes, const FrameParams& P,
                       const OctaveParams* d_oct, const LaunchPlan& plan, uint32_t* scan_key, uint32_t* scan_src,
                       float* scan_cube, int* item_count, int* item_off, surfhip_point* cand, uint32_t* keys,
-                      int* cand_count, int cap, int* status, hipStream_t s, bool stash_trace);
+                      int* cand_count, int cap, int* status, hipStream_t s, bool stash_trace,
+                      const std::function<hipError_t()>* after_scan = nullptr);
 hipError_t launch_sort(const surfhip_point* cand, const uint32_t* keys, uint64_t* gscratch,
                        const int* cand_count, const int* soff, int items_per_frame, int cap, int nframes,
                        surfhip_point* out, int max_pts, int* out_count, int* offsets, int* order, int* status,

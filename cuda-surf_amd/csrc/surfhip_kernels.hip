@@ -16,6 +16,7 @@
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
+#include <string.h>
 #include <stdint.h>
 
 #include <algorithm>
@@ -591,10 +592,37 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(16))) void k_ii
     }
 }
 
+// plan.rsum: the same buffer from the sums k_hess_p0's producers left per
+// 128-column strip and pixel row (own | left << 16, p0_producer RS), no pass
+// over the frames: S_k(r) = the own-column sums of the strips entirely left
+// of X_k = ST k - HALO plus the left-of-X sum of the strip that holds X_k.
+// One thread per frame and pixel row walks the strips once (a wave's loads
+// are 64 consecutive rows of a slab); writes exactly what
+// k_ii_rowseg<ST, HALO> writes: slabs 1 .. ns - 1, rows < H.
+static_assert(p0::XST == hw::ST && p0::XHALO == hw::H, "k_hess_p0 prepares k_hess_w's strips' row sums");
+template <int ST, int HALO>
+__global__ __launch_bounds__(256) void k_rowsum_p0(const uint32_t* __restrict__ psum, int H, int np, int ns,
+                                                   int rs_rows, uint32_t* __restrict__ rowseg)
+{
+    const int f = blockIdx.y, r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= H) return;
+    const uint32_t* in = psum + (size_t)f * np * rs_rows + r;
+    uint32_t* out = rowseg + (size_t)f * ns * rs_rows + r;
+    uint32_t run = 0u;
+    int sp = 0;
+    for (int k = 1; k < ns; k++) {
+        const int sx = (ST * k - HALO) >> 7;                   // the 128-column strip holding X_k
+        if (sx >= np) break;                                   // (never: X_k < W)
+        for (; sp < sx; sp++) run += in[(size_t)sp * rs_rows] & 0xffffu;
+        out[(size_t)k * rs_rows] = run + (in[(size_t)sx * rs_rows] >> 16);
+    }
+}
+
 hipError_t launch_rowseg(const uint8_t* frames, int pitch, long long fstride, int nframes, const FrameParams& P,
                          const LaunchPlan& plan, uint32_t* rowseg, hipStream_t s)
 {
-    if (!plan.iiw || plan.rs_nstrips < 2) return hipSuccess;
+    // (plan.rsum: launch_hessian's octave-0 part makes them)
+    if (!plan.iiw || plan.rs_nstrips < 2 || plan.rsum) return hipSuccess;
     const dim3 g((P.H + 3) / 4, nframes);
     if (plan.iiw == 2)
         k_ii_rowseg<128, 16><<<g, 256, 0, s>>>(frames, pitch, fstride, P.H, plan.rs_nstrips, plan.rs_rows, rowseg);
@@ -727,6 +755,13 @@ void make_plan(const FrameParams& P, const OctaveParams* oct, LaunchPlan& plan, 
         plan.iiw = !on ? 0 : (fv == 2 && plan.p0 == 93) ? 2 : 1;
         plan.rs_rows = 4 * plan.hw_nblk;
         plan.rs_nstrips = plan.iiw == 2 ? plan.q0_strips : plan.hw_nstrips;
+        // k_hess_w's row sums from k_hess_p0's producers instead of
+        // k_ii_rowseg's pass over the frames: k_hess_w writes the integral,
+        // octave 0 runs on the default k_hess_p0 (the RS instantiation) and
+        // there is more than one k_hess_w strip; SURFHIP_ROWSUM=rowseg keeps
+        // the pass (A/B), =p0 is the default
+        const char* re = getenv("SURFHIP_ROWSUM");
+        plan.rsum = plan.iiw == 1 && plan.p0 == 93 && plan.rs_nstrips >= 2 && !(re && !strcmp(re, "rowseg"));
     }
 }
 
@@ -752,6 +787,10 @@ std::string hessian_plan_text(const LaunchPlan& plan, const FrameParams& P)
     // (the row-sum pass runs before the stage: beside the previous batch's
     // NMS when pipelined, like the integral passes it replaces)
     if (plan.iiw) t += plan.iiw == 2 ? ", writing the integral image (k_hess_p0)" : ", writing the integral image";
+    // the writer's row sums: from k_hess_p0's producers (plan.rsum), or the
+    // pass over the frames (a single strip needs none)
+    if (plan.iiw && plan.rs_nstrips >= 2)
+        t += plan.rsum ? ", row sums from k_hess_p0 + k_rowsum_p0" : ", row sums from k_ii_rowseg";
     if (plan.hess_start[kMaxOct] > 0) {
         int lo = -1, hi = -1;
         for (int o = 0; o < P.noct; o++)
@@ -875,7 +914,8 @@ __global__ __launch_bounds__(256) void k_hessian_t0(const int32_t* __restrict__ 
 
 hipError_t launch_hessian(const uint8_t* frames, int pitch, long long fstride, const int32_t* ii, float* resp,
                           int nframes, const FrameParams& P, const OctaveParams* d_oct, const OctaveParams* h_oct,
-                          const LaunchPlan& plan, hipStream_t s, int parts, const uint32_t* rowseg, int32_t* ii_out)
+                          const LaunchPlan& plan, hipStream_t s, int parts, uint32_t* rowseg, int32_t* ii_out,
+                          uint32_t* psum)
 {
     const int nf8 = (nframes + 7) & ~7;
     // parts: 1 = the kernels that read the u8 frames, 2 = those that read the
@@ -915,10 +955,23 @@ hipError_t launch_hessian(const uint8_t* frames, int pitch, long long fstride, c
             const bool wr0 = plan.iiw == 2 && ii_out && rowseg;
 #define P0_CASE(BB, GG)                                                                                          \
     else if (pb == BB && pg == GG) k_hess_p0<BB, GG, SURF_P0_PLANE_NT, false><<<gp, 64 * (1 + GG), 0, s>>>(        \
-        frames, pitch, fstride, resp, P, h_oct[0], plan.q0_strips, nframes, nullptr, nullptr, 0);
+        frames, pitch, fstride, resp, P, h_oct[0], plan.q0_strips, nframes, nullptr, nullptr, 0, nullptr, 0);
+            // (rsum, only with the default 93 and k_hess_w writing the
+            // integral: this launch also leaves its strips' row sums in psum,
+            // k_rowsum_p0 adds them up into rowseg for the k_hess_w launch
+            // that follows on this stream)
+            const bool rs0 = plan.rsum && plan.iiw == 1 && ii_out && rowseg && psum;
             if (wr0 && pb == 9 && pg == 3)
                 k_hess_p0<9, 3, SURF_P0_PLANE_NT, true><<<gp, 64 * 4, 0, s>>>(frames, pitch, fstride, resp, P, h_oct[0],
-                                                               plan.q0_strips, nframes, rowseg, ii_out, plan.rs_rows);
+                                                               plan.q0_strips, nframes, rowseg, ii_out, plan.rs_rows,
+                                                               nullptr, 0);
+            else if (rs0 && pb == 9 && pg == 3) {
+                k_hess_p0<9, 3, SURF_P0_PLANE_NT, false, true><<<gp, 64 * 4, 0, s>>>(
+                    frames, pitch, fstride, resp, P, h_oct[0], plan.q0_strips, nframes, nullptr, nullptr,
+                    plan.rs_rows, psum, plan.hw_nstrips);
+                k_rowsum_p0<hw::ST, hw::H><<<dim3((P.H + 255) / 256, nframes), 256, 0, s>>>(
+                    psum, P.H, plan.q0_strips, plan.rs_nstrips, plan.rs_rows, rowseg);
+            }
             P0_CASE(9, 5) P0_CASE(9, 4) P0_CASE(9, 3) P0_CASE(9, 2) P0_CASE(9, 1) P0_CASE(3, 2) P0_CASE(3, 3)
 #undef P0_CASE
             else if (plan.q0)
@@ -1671,13 +1724,15 @@ __global__ __launch_bounds__(256) void k_nms_fit(const int32_t* __restrict__ ii,
 hipError_t launch_nms(const int32_t* ii, const float* resp, int nframes, const FrameParams& P,
                       const OctaveParams* d_oct, const LaunchPlan& plan, uint32_t* scan_key, uint32_t* scan_src,
                       float* scan_cube, int* item_count, int* item_off, surfhip_point* cand, uint32_t* keys,
-                      int* cand_count, int cap, int* status, hipStream_t s, bool stash_trace)
+                      int* cand_count, int cap, int* status, hipStream_t s, bool stash_trace,
+                      const std::function<hipError_t()>* after_scan)
 {
     const int per = plan.nms_start[kMaxOct];
     if (per == 0) {
         // (no NMS level: nothing to scan; the counters the sort reads are 0)
         hipError_t e = hipMemsetAsync(cand_count, 0, sizeof(int) * (size_t)nframes, s);
         if (e == hipSuccess) e = hipMemsetAsync(status, 0, sizeof(int), s);
+        if (e == hipSuccess && after_scan) e = (*after_scan)();
         return e;
     }
     // the scan's fit records for every batch size (round 5: one 1080p frame's
@@ -1689,6 +1744,10 @@ hipError_t launch_nms(const int32_t* ii, const float* resp, int nframes, const F
     auto* scan = cube ? &k_nms_scan<true> : &k_nms_scan<false>;
     scan<<<dim3(frame_grid(nframes) * per), 256, 0, s>>>(resp, P, d_oct, plan, scan_key, scan_src, scan_cube,
                                                                 item_count, nframes, cand_count, status);
+    if (after_scan) {
+        const hipError_t e = (*after_scan)();
+        if (e != hipSuccess) return e;
+    }
     const int nitems = nframes * per * 4;
     launch_excl_scan(item_count, nitems, item_off, item_off + nitems + 1, s);
     k_nms_fit<<<fit_grid(), 256, 0, s>>>(ii, resp, P, d_oct, scan_key, scan_src, scan_cube, item_off, nitems, per * 4,

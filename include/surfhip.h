@@ -229,6 +229,15 @@ int surfhip_detector_workspace(surfhip_detector* det, int32_t** d_ii, size_t* ii
                                float** d_resp, size_t* resp_stride);
 int surfhip_detector_geometry(surfhip_detector* det, int* iwhp /*3*/, int* swhp /*3*8*/,
                               long long* ooff /*8*/, int* osize /*8*/);
+/* The row sums the integral-writing Hessian kernel adds to its strips'
+ * local integrals, as the last batch left them (parity tests): device
+ * pointer to [max_batch][nstrips][rows] uint32, slab k row r = the sum of
+ * pixel row r over the columns left of writer strip k's first halo column
+ * (slab 0 and rows >= H zero).  *source: 0 = the plan has none (pointer NULL,
+ * counts 0), 1 = k_ii_rowseg's pass over the frames, 2 = k_hess_p0's
+ * producers (+ k_rowsum_p0). */
+int surfhip_detector_rowsums(surfhip_detector* det, uint32_t** d_rowseg, int* nstrips, int* rows,
+                             int* source);
 
 /* Stage-level entry points on frames already resident (parity tests and the
  * Hessian roofline run): integral only, Hessian only.  run_hessian needs a
