@@ -45,6 +45,11 @@ static thread_local hipError_t g_last_hip = hipSuccess;
 
 static inline int align_up(int a, int b) { return (a % b != 0) ? (a - a % b + b) : a; }  // cuda_utils.h:160-163
 
+// How a plan orders its Hessian stage (hessian_stage), and where a call
+// enqueues the next batch's prefetch (prefetch_place)
+enum HessSched { kFused, kIntegralFirst, kSideStream };
+enum Prefetch { kPrefNone, kPrefNms, kPrefDescribe };
+
 struct surfhip_detector {
     int dev = 0;
     int cus = 256;                      // compute units of dev (the describe kernels' persistent grid)
@@ -54,6 +59,7 @@ struct surfhip_detector {
     OctaveParams oct[kMaxOct]{};
     OctaveParams* d_oct = nullptr;      // device copy read by the fused launches
     LaunchPlan plan{};
+    HessSched sched = kFused;
     int W = 0, H = 0, max_batch = 0, max_pts = 0, cap = 0;   // W x H: the frames the integral is taken of
     int srcW = 0, srcH = 0;             // the caller's frames (= W x H unless doubled)
     uint8_t* dbl = nullptr;             // doubled: the (2 srcW - 2) x (2 srcH - 2) frames D
@@ -66,9 +72,8 @@ struct surfhip_detector {
     int icur = 0;                       // iib index of ii
     // prefetched integral (surfhip_detect_batch_next): which frames, in iib[ipref]
     bool pref_valid = false;
-    int ipref = 0, pref_n = 0, pref_pitch = 0;
-    const uint8_t* pref_frames = nullptr;
-    size_t pref_stride = 0;
+    int ipref = 0;
+    FrameBatch pref;
     hipEvent_t fork2 = nullptr;
     float* resp = nullptr;
     uint32_t* colsum = nullptr;
@@ -109,10 +114,7 @@ struct surfhip_detector {
     hipEvent_t desc_ev = nullptr;       // caller's event, recorded before each describe stage
     bool hev_side[SURFHIP_MAX_HESS_EV]{};
     int hev_n = 0;
-    int last_nframes = 0;
-    const uint8_t* last_frames = nullptr;   // u8 source of the last integral (surfhip_run_hessian)
-    int last_pitch = 0;
-    long long last_fstride = 0;
+    FrameBatch last;                    // u8 source of the last integral (surfhip_run_hessian)
     long long hess_bytes = 0;
 };
 
@@ -499,6 +501,9 @@ int surfhip_detector_create(surfhip_detector** out, const surfhip_param* param, 
         if (e != hipSuccess) goto fail;                      \
     } while (0)
     make_plan(d->P, d->oct, d->plan, max_batch);
+    // the u8 kernels write the integral image: one stream; no kernel reads the u8 frames: integral first, one
+    // stream; else: u8 kernels on the detector stream, the integral and the integral-image kernels beside them
+    d->sched = d->plan.iiw ? kFused : !plan_reads_frames(d->plan) ? kIntegralFirst : kSideStream;
     if (d->plan.iiw) {
         // the stage also writes the integral image (read: the u8 frame)
         d->hess_bytes += (long long)d->W * d->H;
@@ -590,44 +595,51 @@ int surfhip_detector_set_stream(surfhip_detector* d, void* stream)
     return SURFHIP_OK;
 }
 
-static int check_frames(surfhip_detector* d, const uint8_t* frames, int nframes, int pitch, size_t stride)
+static int check_frames(surfhip_detector* d, const FrameBatch& b)
 {
-    if (!d || !frames || nframes < 1 || nframes > d->max_batch) return SURFHIP_ERR_INVALID;
-    if (pitch < d->srcW || (pitch & 15) != 0) return SURFHIP_ERR_INVALID;
-    if (((uintptr_t)frames & 15) != 0) return SURFHIP_ERR_INVALID;
-    if (nframes > 1 && (stride < (size_t)pitch * d->srcH || (stride & 15) != 0)) return SURFHIP_ERR_INVALID;
+    if (!d || !b.frames || b.n < 1 || b.n > d->max_batch) return SURFHIP_ERR_INVALID;
+    if (b.pitch < d->srcW || (b.pitch & 15) != 0) return SURFHIP_ERR_INVALID;
+    if (((uintptr_t)b.frames & 15) != 0) return SURFHIP_ERR_INVALID;
+    if (b.n > 1 && (b.stride < (long long)b.pitch * d->srcH || (b.stride & 15) != 0)) return SURFHIP_ERR_INVALID;
     return SURFHIP_OK;
 }
 
 // doubled: upsample the caller's frames into d->dbl and continue from there
-static hipError_t source_frames(surfhip_detector* d, const uint8_t*& frames, int& pitch, size_t& stride,
-                                int nframes, hipStream_t s)
+static hipError_t source_frames(surfhip_detector* d, FrameBatch& b, hipStream_t s)
 {
     if (!d->param.doubled) return hipSuccess;
-    hipError_t e = launch_double(frames, pitch, (long long)stride, nframes, d->srcW, d->srcH, d->dbl, d->dpitch,
-                                 d->dstride, s);
-    frames = d->dbl;
-    pitch = d->dpitch;
-    stride = (size_t)d->dstride;
+    hipError_t e = launch_double(b.frames, b.pitch, b.stride, b.n, d->srcW, d->srcH, d->dbl, d->dpitch, d->dstride, s);
+    b = FrameBatch{d->dbl, b.n, d->dpitch, d->dstride};
     return e;
+}
+
+// Everything queued on the side stream so far is ordered before s's later work
+static hipError_t side_before(surfhip_detector* d, hipStream_t s)
+{
+    hipError_t e = hipEventRecord(d->join, d->side);
+    return e == hipSuccess ? hipStreamWaitEvent(s, d->join, 0) : e;
+}
+
+// (plan.iiw: the stage writes the integral image it is given, d->ii)
+static HessianArgs hessian_args(surfhip_detector* d, const FrameBatch& b)
+{
+    return {b, d->ii, d->resp, &d->P, d->d_oct, d->oct, &d->plan, d->rowseg, d->plan.iiw ? d->ii : nullptr, d->psum};
 }
 
 int surfhip_run_integral(surfhip_detector* d, const uint8_t* frames, int nframes, int pitch, size_t stride)
 {
-    int rc = check_frames(d, frames, nframes, pitch, stride);
+    FrameBatch b{frames, nframes, pitch, (long long)stride};
+    int rc = check_frames(d, b);
     if (rc) return rc;
     // a prefetch on the side stream may still be using the colsum scratch
-    HIPCHK(hipEventRecord(d->join, d->side));
-    HIPCHK(hipStreamWaitEvent(d->stream, d->join, 0));
-    HIPCHK(source_frames(d, frames, pitch, stride, nframes, d->stream));
-    HIPCHK(launch_integral(frames, pitch, (long long)stride, nframes, d->P, d->colsum, d->ii, d->stream));
+    HIPCHK(side_before(d, d->stream));
+    HIPCHK(source_frames(d, b, d->stream));
+    HIPCHK(launch_integral(b, d->P, d->colsum, d->ii, d->stream));
     // (plan.iiw) the row sums a following run_hessian's k_hess_w adds: it
     // rewrites the same integral image
-    HIPCHK(launch_rowseg(frames, pitch, (long long)stride, nframes, d->P, d->plan, d->rowseg, d->stream));
+    HIPCHK(launch_rowseg(b, d->P, d->plan, d->rowseg, d->stream));
     d->pref_valid = false;
-    d->last_frames = frames;
-    d->last_pitch = pitch;
-    d->last_fstride = (long long)stride;
+    d->last = b;
     return SURFHIP_OK;
 }
 
@@ -635,76 +647,55 @@ int surfhip_run_hessian(surfhip_detector* d, int nframes)
 {
     if (!d || nframes < 1 || nframes > d->max_batch) return SURFHIP_ERR_INVALID;
     // the u8 Hessian kernels read the frames of the last run_integral
-    if (!d->last_frames && plan_reads_frames(d->plan)) return SURFHIP_ERR_INVALID;
-    HIPCHK(launch_hessian(d->last_frames, d->last_pitch, d->last_fstride, d->ii, d->resp, nframes, d->P, d->d_oct,
-                          d->oct, d->plan, d->stream, 3, d->rowseg, d->ii, d->psum));
+    if (!d->last.frames && plan_reads_frames(d->plan)) return SURFHIP_ERR_INVALID;
+    FrameBatch b = d->last;
+    b.n = nframes;
+    const HessianArgs a = hessian_args(d, b);
+    HIPCHK(launch_hess_oct0(a, d->stream));
+    HIPCHK(launch_hess_w(a, d->stream));
+    HIPCHK(launch_hess_ii(a, d->stream));
     return SURFHIP_OK;
 }
 
-// The second integral buffer is allocated on first use of the pipelined
-// entry point (a plain detect_batch caller never pays for it).
-static hipError_t ensure_second_ii(surfhip_detector* d)
+// This batch's integral buffer: the one the previous call prefetched into (`have`), else the current
+// one; a fused plan's Hessian writes the integral itself, into buffer 0.  The second buffer is allocated
+// on first use of the pipelined entry point (a plain detect_batch caller never pays for it).
+static hipError_t pick_integral(surfhip_detector* d, bool have, bool pipe)
 {
-    if (d->iib[1]) return hipSuccess;
-    const size_t bytes = (size_t)d->max_batch * d->P.ii_stride * sizeof(int32_t);
-    hipError_t e = hipMalloc((void**)&d->iib[1], bytes);
-    if (e == hipSuccess) e = hipMemset(d->iib[1], 0, bytes);     // pad columns stay 0
-    return e;
-}
-
-int surfhip_detect_batch_next(surfhip_detector* d, const uint8_t* frames, int nframes, int pitch, size_t stride,
-                              surfhip_point* points, float* desc, int* counts, const uint8_t* next_frames,
-                              int next_nframes, int next_pitch, size_t next_stride)
-{
-    int rc = check_frames(d, frames, nframes, pitch, stride);
-    if (rc) return rc;
-    if (!points || !counts) return SURFHIP_ERR_INVALID;
-    // no prefetch for doubled frames (the upsampled frames share one scratch
-    // buffer) or while stage profiling (serial stages)
-    const bool pipe = next_frames != nullptr && !d->param.doubled && !d->profiling;
-    if (next_frames && !d->param.doubled) {
-        rc = check_frames(d, next_frames, next_nframes, next_pitch, next_stride);
-        if (rc) return rc;
+    if (pipe && d->sched != kFused && !d->iib[1]) {
+        const size_t bytes = (size_t)d->max_batch * d->P.ii_stride * sizeof(int32_t);
+        hipError_t e = hipMalloc((void**)&d->iib[1], bytes);
+        if (e == hipSuccess) e = hipMemset(d->iib[1], 0, bytes);     // pad columns stay 0
+        if (e != hipSuccess) return e;
     }
-    // (plan.iiw: the integral is written by this batch's Hessian, one buffer)
-    const bool iiw = d->plan.iiw != 0;
-    if (pipe && !iiw) HIPCHK(ensure_second_ii(d));
-    hipStream_t s = d->stream;
-    const bool prof = d->profiling;
-    // this batch's integral (iiw: its row sums): prefetched by the previous
-    // call (same frames), or computed now
-    const bool have = !prof && d->pref_valid && d->pref_frames == frames && d->pref_n == nframes &&
-                      d->pref_pitch == pitch && d->pref_stride == stride;
-    d->icur = (have && !iiw) ? d->ipref : (iiw ? 0 : d->icur);
+    d->icur = d->sched == kFused ? 0 : have ? d->ipref : d->icur;
     d->ii = d->iib[d->icur];
     d->pref_valid = false;
-    // (the per-batch counters -- accepted candidates per frame, the
-    // truncation flag, the scan items' survivor counts -- are written by the
-    // NMS scan itself: no memsets ahead of the Hessian)
-    if (prof) {
-        // serial, so that the stage events bracket each stage alone; a
-        // prefetch left on the side stream by an earlier pipelined call may
-        // still be using the colsum scratch the integral below reuses
-        HIPCHK(hipEventRecord(d->join, d->side));
-        HIPCHK(hipStreamWaitEvent(s, d->join, 0));
-        HIPCHK(hipEventRecord(d->ev[0], s));
-        HIPCHK(source_frames(d, frames, pitch, stride, nframes, s));
-        if (iiw) HIPCHK(launch_rowseg(frames, pitch, (long long)stride, nframes, d->P, d->plan, d->rowseg, s));
-        else HIPCHK(launch_integral(frames, pitch, (long long)stride, nframes, d->P, d->colsum, d->ii, s));
-        HIPCHK(hipEventRecord(d->ev[1], s));
-        HIPCHK(launch_hessian(frames, pitch, (long long)stride, d->ii, d->resp, nframes, d->P, d->d_oct, d->oct,
-                              d->plan, s, 3, d->rowseg, d->ii, d->psum));
-        HIPCHK(hipEventRecord(d->ev[2], s));
-    } else {
-        // In-step Hessian timing brackets the WHOLE stage: from the fork (on
-        // s) to the end of the u8 kernels on s and of the integral-image
-        // kernels on the side stream, whichever is later
-        // (surfhip_detector_hessian_times).  Without a prefetched integral
-        // the side stream's part starts after the integral, which the
-        // bracket then includes.
-        HIPCHK(source_frames(d, frames, pitch, stride, nframes, s));
-        const bool th = d->time_hess && d->hev_n < SURFHIP_MAX_HESS_EV;
-        if (iiw) {
+    return hipSuccess;
+}
+
+// The Hessian stage of batch a.b: its integral image (fused: its row sums) unless the previous call
+// prefetched it (`have`), and its response planes; the detector stream s ends up ordered after all of it.
+// Profiled: serial on s, so that the stage events bracket each stage alone (ev[1] between the integral /
+// row-sum pass and the Hessian kernels); the caller ordered the side stream before ev[0].
+// In-step timing brackets the WHOLE stage: from hev[0] to the end of the kernels on s and of the
+// integral-image kernels on the side stream, whichever is later (surfhip_detector_hessian_times).  Without
+// a prefetched integral the side stream's part starts after the integral, which the bracket then includes.
+static int hessian_stage(surfhip_detector* d, const HessianArgs& a, bool have)
+{
+    hipStream_t s = d->stream;
+    const bool prof = d->profiling;
+    const bool timed = !prof && d->time_hess && d->hev_n < SURFHIP_MAX_HESS_EV;
+    hipEvent_t* hev = d->hev[timed ? d->hev_n : 0];
+    const hipEvent_t begin = timed ? hev[0] : nullptr, mid = prof ? d->ev[1] : nullptr;
+    const hipEvent_t end = timed ? hev[1] : prof ? d->ev[2] : nullptr;
+    auto mark = [](hipEvent_t ev, hipStream_t st) { return ev ? hipEventRecord(ev, st) : hipSuccess; };
+    // (profiled: a side-stream plan runs integral first, everything on s)
+    const HessSched sched = prof && d->sched == kSideStream ? kIntegralFirst : d->sched;
+    const bool side_hess = sched == kSideStream && d->plan.hess_start[kMaxOct] > 0;
+    const bool late = sched == kFused && have && d->plan.iiw != 2;
+    switch (sched) {
+        case kFused:
             // octaves 0-3 on the u8 kernels, the integral image written by
             // k_hess_w, any later octave's k_hessian after them (it reads
             // that integral): one stream.  The side stream's last work (a
@@ -713,24 +704,16 @@ int surfhip_detect_batch_next(surfhip_detector* d, const uint8_t* frames, int nf
             // the octave-0 kernel and k_hess_w, where the wait's latency
             // hides behind the running octave-0 kernel (iiw 2: the octave-0
             // kernel writes the integral, so the wait precedes it).
-            const bool p0w = d->plan.iiw == 2;
-            HIPCHK(hipEventRecord(d->join, d->side));
-            if (!have || p0w) HIPCHK(hipStreamWaitEvent(s, d->join, 0));
-            if (!have)
-                HIPCHK(launch_rowseg(frames, pitch, (long long)stride, nframes, d->P, d->plan, d->rowseg, s));
-            if (th) HIPCHK(hipEventRecord(d->hev[d->hev_n][0], s));
-            HIPCHK(launch_hessian(frames, pitch, (long long)stride, d->ii, d->resp, nframes, d->P, d->d_oct, d->oct,
-                                  d->plan, s, 4, d->rowseg, d->ii, d->psum));
-            if (have && !p0w) HIPCHK(hipStreamWaitEvent(s, d->join, 0));
-            HIPCHK(launch_hessian(frames, pitch, (long long)stride, d->ii, d->resp, nframes, d->P, d->d_oct, d->oct,
-                                  d->plan, s, 8 | 2, d->rowseg, d->ii, d->psum));
-            if (th) {
-                HIPCHK(hipEventRecord(d->hev[d->hev_n][1], s));
-                d->hev_side[d->hev_n++] = false;
-            }
-        } else {
-        if (th) HIPCHK(hipEventRecord(d->hev[d->hev_n][0], s));
-        if (!plan_reads_frames(d->plan)) {
+            if (!prof && !late) HIPCHK(side_before(d, s));
+            if (!have) HIPCHK(launch_rowseg(a.b, d->P, d->plan, d->rowseg, s));
+            HIPCHK(mark(mid, s));
+            HIPCHK(mark(begin, s));
+            HIPCHK(launch_hess_oct0(a, s));
+            if (late) HIPCHK(side_before(d, s));
+            HIPCHK(launch_hess_w(a, s));
+            HIPCHK(launch_hess_ii(a, s));
+            break;
+        case kIntegralFirst:
             // Every Hessian kernel reads the integral image (the gather plan
             // of batches <= kGatherBatch, config #2): nothing would run beside
             // them, so they stay on the detector stream -- the fork / join
@@ -738,104 +721,117 @@ int surfhip_detect_batch_next(surfhip_detector* d, const uint8_t* frames, int nf
             // of idle GPU in a kernel trace (profiles/r05ac2_*).  The side
             // stream's last work (a prefetch into d->ii, or one using the
             // colsum scratch) is ordered first; it finished long ago.
-            HIPCHK(hipEventRecord(d->join, d->side));
-            HIPCHK(hipStreamWaitEvent(s, d->join, 0));
-            if (!have)
-                HIPCHK(launch_integral(frames, pitch, (long long)stride, nframes, d->P, d->colsum, d->ii, s));
-            HIPCHK(launch_hessian(frames, pitch, (long long)stride, d->ii, d->resp, nframes, d->P, d->d_oct,
-                                  d->oct, d->plan, s, 2));
-            if (th) {
-                HIPCHK(hipEventRecord(d->hev[d->hev_n][1], s));
-                d->hev_side[d->hev_n++] = false;
-            }
-        } else {
+            HIPCHK(mark(begin, s));
+            if (!prof) HIPCHK(side_before(d, s));
+            if (!have) HIPCHK(launch_integral(a.b, d->P, d->colsum, d->ii, s));
+            HIPCHK(mark(mid, s));
+            if (prof) HIPCHK(launch_hess_oct0(a, s));        // (the plan's own u8 launches are empty)
+            if (prof) HIPCHK(launch_hess_w(a, s));
+            HIPCHK(launch_hess_ii(a, s));
+            break;
+        case kSideStream:
             // the u8 Hessian kernels need no integral image: they run on s;
             // the integral (unless prefetched) and the integral-image Hessian
             // kernels run on the side stream beside them; s waits for both
             // before NMS
-            const bool side_hess = d->plan.hess_start[kMaxOct] > 0;
+            HIPCHK(mark(begin, s));
             HIPCHK(hipEventRecord(d->fork, s));
             HIPCHK(hipStreamWaitEvent(d->side, d->fork, 0));
-            if (!have)
-                HIPCHK(launch_integral(frames, pitch, (long long)stride, nframes, d->P, d->colsum, d->ii, d->side));
-            HIPCHK(launch_hessian(frames, pitch, (long long)stride, d->ii, d->resp, nframes, d->P, d->d_oct,
-                                  d->oct, d->plan, d->side, 2));
-            if (th && side_hess) HIPCHK(hipEventRecord(d->hev[d->hev_n][2], d->side));
-            HIPCHK(hipEventRecord(d->join, d->side));
-            HIPCHK(launch_hessian(frames, pitch, (long long)stride, d->ii, d->resp, nframes, d->P, d->d_oct,
-                                  d->oct, d->plan, s, 1));
-            if (th) {
-                HIPCHK(hipEventRecord(d->hev[d->hev_n][1], s));
-                d->hev_side[d->hev_n++] = side_hess;
-            }
-            HIPCHK(hipStreamWaitEvent(s, d->join, 0));
-        }
-        }
+            if (!have) HIPCHK(launch_integral(a.b, d->P, d->colsum, d->ii, d->side));
+            HIPCHK(launch_hess_ii(a, d->side));
+            if (timed && side_hess) HIPCHK(hipEventRecord(hev[2], d->side));
+            HIPCHK(launch_hess_oct0(a, s));
+            HIPCHK(launch_hess_w(a, s));
+            break;
     }
-    // The next batch's integral (into the other buffer) on the side stream,
-    // ordered after everything on s so far, so that buffer's last readers
-    // (the previous batch's fit and describe) are done.  Default: forked
-    // after this batch's Hessian, beside its NMS scan, fit and sort (the
-    // Hessian and describe then run alone); SURFHIP_PREFETCH=describe forks
-    // it after the sort instead, beside describe.  With the integral written
-    // by k_hess_w (iiw) the prefetch is only the row-sum pass and the default
-    // is beside describe (its HBM use is low and its waves leave room).
-    auto prefetch_next = [&]() -> hipError_t {
-        const int nx = d->icur ^ 1;
-        hipError_t e = hipEventRecord(d->fork2, s);
-        if (e == hipSuccess) e = hipStreamWaitEvent(d->side, d->fork2, 0);
-        // (iiw: the next batch's row sums; this batch's k_hess_w has read d->rowseg)
-        if (e == hipSuccess && iiw)
-            e = launch_rowseg(next_frames, next_pitch, (long long)next_stride, next_nframes, d->P, d->plan,
-                              d->rowseg, d->side);
-        else if (e == hipSuccess)
-            e = launch_integral(next_frames, next_pitch, (long long)next_stride, next_nframes, d->P, d->colsum,
-                                d->iib[nx], d->side);
-        if (e != hipSuccess) return e;
-        d->pref_valid = true;
-        d->ipref = nx;
-        d->pref_frames = next_frames;
-        d->pref_n = next_nframes;
-        d->pref_pitch = next_pitch;
-        d->pref_stride = next_stride;
-        return hipSuccess;
-    };
-    // (iiw: the prefetch is the row-sum pass, default beside describe, whose
-    // waves leave room for its 16-VGPR waves; SURFHIP_PREFETCH=nms / describe
-    // / tail.  tail (iiw only, elsewhere nms): forked right after k_nms_scan,
-    // beside the small grids of the scan's prefix, the fit, the sort and the
-    // worklist, which leave most of the chip empty.  plan.rsum: k_hess_p0
-    // makes the row sums of its own batch, nothing to prefetch)
-    static const int pref_env = [] {
-        const char* e = getenv("SURFHIP_PREFETCH");
-        return !e ? -1 : !strcmp(e, "describe") ? 0 : !strcmp(e, "tail") ? 2 : 1;
-    }();
-    const bool pref_on = pipe && !(iiw && d->plan.rsum);
-    const bool pref_tail = iiw && pref_env == 2;
-    const bool pref_nms = !pref_tail && (pref_env < 0 ? !iiw : pref_env >= 1);
-    if (pref_on && pref_nms) HIPCHK(prefetch_next());
-    std::function<hipError_t()> after_scan;
-    if (pref_on && pref_tail) after_scan = prefetch_next;
+    HIPCHK(mark(end, s));
+    if (sched == kSideStream) HIPCHK(side_before(d, s));
+    if (timed) d->hev_side[d->hev_n++] = side_hess;
+    return SURFHIP_OK;
+}
+
+// Where this call enqueues the next batch's prefetch.  Default: after this batch's Hessian, beside its NMS
+// scan, fit and sort (the Hessian and describe then run alone); a fused plan's prefetch is only the row-sum
+// pass and its default is before describe (its HBM use is low and describe's waves leave room for its
+// 16-VGPR waves).  SURFHIP_PREFETCH=describe / any other value (nms) overrides the default.  plan.rsum:
+// k_hess_p0 makes the row sums of its own batch, nothing to prefetch.
+static Prefetch prefetch_place(const LaunchPlan& plan, bool pipe)
+{
+    static const char* const env = getenv("SURFHIP_PREFETCH");
+    if (!pipe || (plan.iiw && plan.rsum)) return kPrefNone;
+    return (env ? strcmp(env, "describe") != 0 : !plan.iiw) ? kPrefNms : kPrefDescribe;
+}
+
+// The next batch's integral (into the other buffer; fused: its row sums) on the side stream, ordered after
+// everything on s so far, so that buffer's last readers (the previous batch's fit and describe; fused: this
+// batch's k_hess_w of d->rowseg) are done.
+static hipError_t prefetch_next(surfhip_detector* d, const FrameBatch& next, hipStream_t s)
+{
+    const int nx = d->icur ^ 1;
+    hipError_t e = hipEventRecord(d->fork2, s);
+    if (e == hipSuccess) e = hipStreamWaitEvent(d->side, d->fork2, 0);
+    if (e == hipSuccess)
+        e = d->sched == kFused ? launch_rowseg(next, d->P, d->plan, d->rowseg, d->side)
+                               : launch_integral(next, d->P, d->colsum, d->iib[nx], d->side);
+    if (e != hipSuccess) return e;
+    d->pref_valid = true;
+    d->ipref = nx;
+    d->pref = next;
+    return hipSuccess;
+}
+
+int surfhip_detect_batch_next(surfhip_detector* d, const uint8_t* frames, int nframes, int pitch, size_t stride,
+                              surfhip_point* points, float* desc, int* counts, const uint8_t* next_frames,
+                              int next_nframes, int next_pitch, size_t next_stride)
+{
+    FrameBatch b{frames, nframes, pitch, (long long)stride};
+    const FrameBatch next{next_frames, next_nframes, next_pitch, (long long)next_stride};
+    int rc = check_frames(d, b);
+    if (rc) return rc;
+    if (!points || !counts) return SURFHIP_ERR_INVALID;
+    // no prefetch for doubled frames (the upsampled frames share one scratch
+    // buffer) or while stage profiling (serial stages)
+    const bool prof = d->profiling;
+    const bool pipe = next.frames != nullptr && !d->param.doubled && !prof;
+    if (next.frames && !d->param.doubled) {
+        rc = check_frames(d, next);
+        if (rc) return rc;
+    }
+    const Prefetch pf = prefetch_place(d->plan, pipe);
+    hipStream_t s = d->stream;
+    // this batch's integral (fused: its row sums): prefetched by the previous
+    // call (same frames), or computed now
+    const bool have = !prof && d->pref_valid && d->pref == b;
+    HIPCHK(pick_integral(d, have, pipe));
+    // (the per-batch counters -- accepted candidates per frame, the
+    // truncation flag, the scan items' survivor counts -- are written by the
+    // NMS scan itself: no memsets ahead of the Hessian)
+    if (prof) {
+        // a prefetch left on the side stream by an earlier pipelined call may
+        // still be using the colsum scratch the integral reuses
+        HIPCHK(side_before(d, s));
+        HIPCHK(hipEventRecord(d->ev[0], s));
+    }
+    HIPCHK(source_frames(d, b, s));
+    rc = hessian_stage(d, hessian_args(d, b), have);
+    if (rc) return rc;
+    if (pf == kPrefNms) HIPCHK(prefetch_next(d, next, s));
     // getTrace in k_describe_u2 (its integral rows are in L2 there) rather
     // than in the fit (16 scattered integral loads per survivor from HBM)
     const bool trace_desc = desc && trace_in_describe(d->P, nframes);
     HIPCHK(launch_nms(d->ii, d->resp, nframes, d->P, d->d_oct, d->plan, d->scan_key, d->scan_src, d->scan_cube,
-                      d->item_count, d->item_off, d->cand, d->keys, d->cand_count, d->cap, d->status, s, trace_desc,
-                      after_scan ? &after_scan : nullptr));
+                      d->item_count, d->item_off, d->cand, d->keys, d->cand_count, d->cap, d->status, s, trace_desc));
     if (prof) HIPCHK(hipEventRecord(d->ev[3], s));
     HIPCHK(launch_sort(d->cand, d->keys, d->gscratch, d->cand_count, d->item_off, d->plan.nms_start[kMaxOct] * 4,
                        d->cap, nframes, points, d->max_pts, counts, d->offsets, d->order, d->status, s));
     if (prof) HIPCHK(hipEventRecord(d->ev[4], s));
-    if (pref_on && !pref_nms && !pref_tail) HIPCHK(prefetch_next());
+    if (pf == kPrefDescribe) HIPCHK(prefetch_next(d, next, s));
     if (d->desc_ev) HIPCHK(hipEventRecord(d->desc_ev, s));
     if (desc)
         HIPCHK(launch_describe(d->ii, d->P, points, d->max_pts, counts, d->offsets, d->order, d->work, nframes, desc,
-                               d->status + 64, s, pref_on && !pref_nms && !iiw, d->cus, trace_desc));
+                               d->status + 64, s, pf == kPrefDescribe && !d->plan.iiw, d->cus, trace_desc));
     if (prof) HIPCHK(hipEventRecord(d->ev[5], s));
-    d->last_nframes = nframes;
-    d->last_frames = frames;
-    d->last_pitch = pitch;
-    d->last_fstride = (long long)stride;
+    d->last = b;
     return SURFHIP_OK;
 }
 
@@ -849,11 +845,8 @@ int surfhip_detector_set_describe_event(surfhip_detector* d, void* ev)
 int surfhip_detector_drain(surfhip_detector* d)
 {
     if (!d) return SURFHIP_ERR_INVALID;
-    // everything queued on the side stream so far (a prefetch of the next
-    // batch's integral, which reads next_frames) is ordered before the
-    // detector stream's later work
-    HIPCHK(hipEventRecord(d->join, d->side));
-    HIPCHK(hipStreamWaitEvent(d->stream, d->join, 0));
+    // (a prefetch of the next batch's integral, which reads next_frames)
+    HIPCHK(side_before(d, d->stream));
     return SURFHIP_OK;
 }
 

@@ -12,7 +12,6 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#include <functional>
 #include <string>
 
 #include "surfhip.h"
@@ -106,8 +105,17 @@ struct Tables {
 // ---- launch helpers (defined in surfhip_kernels.hip) -------------------
 hipError_t set_tables(const Tables& t);
 
-hipError_t launch_integral(const uint8_t* frames, int pitch, long long fstride, int nframes,
-                           const FrameParams& P, uint32_t* colsum, int32_t* ii, hipStream_t s);
+// A batch of u8 frames: n frames `stride` bytes apart, their rows `pitch` apart
+struct FrameBatch {
+    const uint8_t* frames = nullptr;
+    int n = 0, pitch = 0;
+    long long stride = 0;           // one integer type inside the library (the C-ABI's is size_t)
+};
+inline bool operator==(const FrameBatch& a, const FrameBatch& b)
+{
+    return a.frames == b.frames && a.n == b.n && a.pitch == b.pitch && a.stride == b.stride;
+}
+hipError_t launch_integral(const FrameBatch& b, const FrameParams& P, uint32_t* colsum, int32_t* ii, hipStream_t s);
 // Block ranges of the fused all-octave launches and the Hessian kernel of
 // each octave (computed once per detector; make_plan).
 struct LaunchPlan {
@@ -150,33 +158,37 @@ void make_plan(const FrameParams& P, const OctaveParams* oct, LaunchPlan& plan, 
 // the Hessian stage's kernels of a plan, as text (surfhip_hessian_plan)
 std::string hessian_plan_text(const LaunchPlan& plan, const FrameParams& P);
 
-// parts: 1 = the u8-frame kernels (frames must be given), 2 = the
-// integral-image kernel (k_hessian), 3 = both; 4 / 8 = only the octave-0 /
-// only the k_hess_w launch of part 1.  ii_out + rowseg (plan.iiw):
-// k_hess_w (iiw 1) or k_hess_p0 (iiw 2) writes the frames' integral image
-// into ii_out (rowseg: the k_ii_rowseg sums of the same frames); nullptr:
-// neither does.  psum (plan.rsum): nframes x q0_strips x rs_rows uint32 of
-// scratch; the octave-0 part then fills rowseg itself (k_hess_p0's strip
-// sums, k_rowsum_p0) and launch_rowseg does nothing.
-hipError_t launch_hessian(const uint8_t* frames, int pitch, long long fstride, const int32_t* ii, float* resp,
-                          int nframes, const FrameParams& P, const OctaveParams* d_oct, const OctaveParams* h_oct,
-                          const LaunchPlan& plan, hipStream_t s, int parts = 3, uint32_t* rowseg = nullptr,
-                          int32_t* ii_out = nullptr, uint32_t* psum = nullptr);
-// plan.iiw: the row sums the writer's strips add to their integral (rowseg:
-// nframes x rs_nstrips x rs_rows uint32; slab 0 and rows >= H stay zero)
-// (plan.rsum: no launch)
-hipError_t launch_rowseg(const uint8_t* frames, int pitch, long long fstride, int nframes, const FrameParams& P,
-                         const LaunchPlan& plan, uint32_t* rowseg, hipStream_t s);
+// The Hessian stage's launches of one batch, in the order one stream runs them.  The first two read the u8
+// frames (b.frames must be given where the plan has such kernels), the third reads ii: two streams may run them.
+struct HessianArgs {
+    FrameBatch b;
+    const int32_t* ii;
+    float* resp;
+    const FrameParams* P;
+    const OctaveParams *d_oct, *h_oct;
+    const LaunchPlan* plan;
+    // plan.iiw: k_hess_w (iiw 1) or k_hess_p0 (iiw 2) writes the frames' integral image into ii_out, adding
+    // the row sums in rowseg (nframes x rs_nstrips x rs_rows uint32; slab 0 and rows >= H stay zero); nullptr:
+    // neither does.  psum (plan.rsum): nframes x q0_strips x rs_rows uint32 of scratch; the octave-0 launch
+    // then fills rowseg itself (k_hess_p0's strip sums, k_rowsum_p0).
+    uint32_t* rowseg;
+    int32_t* ii_out;
+    uint32_t* psum;
+};
+// k_hess_q01, or k_hess_p0 (+ k_rowsum_p0: plan.rsum), or k_hess_q0; then k_hess_q1 where the plan has it
+hipError_t launch_hess_oct0(const HessianArgs& a, hipStream_t s);
+hipError_t launch_hess_w(const HessianArgs& a, hipStream_t s);      // octaves 1 .. plan.hw_n on k_hess_w
+hipError_t launch_hess_ii(const HessianArgs& a, hipStream_t s);     // k_hessian_t0, k_hessian
+// plan.iiw without plan.rsum: rowseg of the batch by k_ii_rowseg's pass over its frames; else no launch
+hipError_t launch_rowseg(const FrameBatch& b, const FrameParams& P, const LaunchPlan& plan, uint32_t* rowseg,
+                         hipStream_t s);
 // NMS scan items: one wave's 64 block columns x kScanRows / 4 block rows;
 // each item owns kItemCap survivor slots (no atomics in the scan).
 // (also zeroes cand_count[0, nframes) and *status, the per-batch counters)
-// after_scan: called once k_nms_scan is queued, before the scan's prefix and
-// the fit (the caller forks a side stream there)
 hipError_t launch_nms(const int32_t* ii, const float* resp, int nframes, const FrameParams& P,
                       const OctaveParams* d_oct, const LaunchPlan& plan, uint32_t* scan_key, uint32_t* scan_src,
                       float* scan_cube, int* item_count, int* item_off, surfhip_point* cand, uint32_t* keys,
-                      int* cand_count, int cap, int* status, hipStream_t s, bool stash_trace,
-                      const std::function<hipError_t()>* after_scan = nullptr);
+                      int* cand_count, int cap, int* status, hipStream_t s, bool stash_trace);
 hipError_t launch_sort(const surfhip_point* cand, const uint32_t* keys, uint64_t* gscratch,
                        const int* cand_count, const int* soff, int items_per_frame, int cap, int nframes,
                        surfhip_point* out, int max_pts, int* out_count, int* offsets, int* order, int* status,
@@ -184,8 +196,8 @@ hipError_t launch_sort(const surfhip_point* cand, const uint32_t* keys, uint64_t
 hipError_t set_max_lds(const void* fn, int bytes);
 // queue: kDescQueueBytes of device scratch (the per-XCD work counters of
 // k_describe_ur, 8 x kDescQ of them 256 B apart, zeroed by the launch)
-// beside: another stream's kernels (the next batch's integral) run beside
-// it, so the persistent grid leaves each CU a workgroup slot
+// beside: another stream's kernels (the next batch's integral, not a mere
+// row-sum pass) run beside it, so the persistent grid leaves each CU a workgroup slot
 // work: max_batch * max_pts * kWorkF4 float4 of scratch (k_describe_u2's flattened schedule)
 // cus: compute units of the detector's device (sizes the persistent grid)
 // trace: the fit left getTrace to the describe (trace_in_describe, the same

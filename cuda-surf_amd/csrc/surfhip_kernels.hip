@@ -467,35 +467,34 @@ static void launch_bandscan(uint32_t* colsum, int nbands, int CW, int W, int nfr
     else k_ii_bandscan<272><<<dim3((W + 255) / 256, nframes), 256, 0, s>>>(colsum, nbands, CW, W);
 }
 
-hipError_t launch_integral(const uint8_t* frames, int pitch, long long fstride, int nframes,
-                           const FrameParams& P, uint32_t* colsum, int32_t* ii, hipStream_t s)
+hipError_t launch_integral(const FrameBatch& b, const FrameParams& P, uint32_t* colsum, int32_t* ii, hipStream_t s)
 {
     // small batches: 8-row bands (4x the band waves of the fill pass, which
     // is one wave per band) -- colsum is sized for both (integral_bands())
-    const int br = nframes <= kSmallBatch ? small_band_rows() : big_band_rows();
+    const int br = b.n <= kSmallBatch ? small_band_rows() : big_band_rows();
     const int nbands = (P.H + br - 1) / br;
     const int W = P.W;
-    dim3 grid(nbands, nframes);
+    dim3 grid(nbands, b.n);
     if (W + 1 <= 2048) {
         const int CW = 2048;
-        k_ii_bandsum<8><<<grid, 256, 0, s>>>(frames, pitch, fstride, W, P.H, nbands, colsum, CW, br);
-        launch_bandscan(colsum, nbands, CW, W, nframes, s);
-        k_ii_fill_w<8><<<(nbands * nframes + 3) / 4, 256, 0, s>>>(frames, pitch, fstride, W, P.H, nbands, colsum, CW,
-                                                                    ii, P.ip, P.ii_stride, nframes, br);
+        k_ii_bandsum<8><<<grid, 256, 0, s>>>(b.frames, b.pitch, b.stride, W, P.H, nbands, colsum, CW, br);
+        launch_bandscan(colsum, nbands, CW, W, b.n, s);
+        k_ii_fill_w<8><<<(nbands * b.n + 3) / 4, 256, 0, s>>>(b.frames, b.pitch, b.stride, W, P.H, nbands, colsum, CW,
+                                                                    ii, P.ip, P.ii_stride, b.n, br);
     } else if (W + 1 <= 4096) {
         const int CW = 4096;
-        k_ii_bandsum<16><<<grid, 256, 0, s>>>(frames, pitch, fstride, W, P.H, nbands, colsum, CW, br);
-        launch_bandscan(colsum, nbands, CW, W, nframes, s);
-        k_ii_fill_w<16><<<(nbands * nframes + 3) / 4, 256, 0, s>>>(frames, pitch, fstride, W, P.H, nbands, colsum,
-                                                                     CW, ii, P.ip, P.ii_stride, nframes, br);
+        k_ii_bandsum<16><<<grid, 256, 0, s>>>(b.frames, b.pitch, b.stride, W, P.H, nbands, colsum, CW, br);
+        launch_bandscan(colsum, nbands, CW, W, b.n, s);
+        k_ii_fill_w<16><<<(nbands * b.n + 3) / 4, 256, 0, s>>>(b.frames, b.pitch, b.stride, W, P.H, nbands, colsum,
+                                                                     CW, ii, P.ip, P.ii_stride, b.n, br);
     } else if (W + 1 <= 8192) {
         // wide frames (up to 8,191 columns): 32 columns per thread, the
         // workgroup-scan fill (one 256-thread block per band, two barriers a row)
         const int CW = 8192;
-        k_ii_bandsum<32><<<grid, 256, 0, s>>>(frames, pitch, fstride, W, P.H, nbands, colsum, CW, br);
-        launch_bandscan(colsum, nbands, CW, W, nframes, s);
-        k_ii_fill<32><<<grid, 256, 0, s>>>(frames, pitch, fstride, W, P.H, nbands, colsum, CW, ii, P.ip, P.ii_stride,
-                                           br);
+        k_ii_bandsum<32><<<grid, 256, 0, s>>>(b.frames, b.pitch, b.stride, W, P.H, nbands, colsum, CW, br);
+        launch_bandscan(colsum, nbands, CW, W, b.n, s);
+        k_ii_fill<32><<<grid, 256, 0, s>>>(b.frames, b.pitch, b.stride, W, P.H, nbands, colsum, CW, ii, P.ip,
+                                           P.ii_stride, br);
     } else {
         return hipErrorInvalidValue;
     }
@@ -618,16 +617,16 @@ __global__ __launch_bounds__(256) void k_rowsum_p0(const uint32_t* __restrict__ 
     }
 }
 
-hipError_t launch_rowseg(const uint8_t* frames, int pitch, long long fstride, int nframes, const FrameParams& P,
-                         const LaunchPlan& plan, uint32_t* rowseg, hipStream_t s)
+hipError_t launch_rowseg(const FrameBatch& b, const FrameParams& P, const LaunchPlan& plan, uint32_t* rowseg,
+                         hipStream_t s)
 {
-    // (plan.rsum: launch_hessian's octave-0 part makes them)
+    // (plan.rsum: launch_hess_oct0 makes them)
     if (!plan.iiw || plan.rs_nstrips < 2 || plan.rsum) return hipSuccess;
-    const dim3 g((P.H + 3) / 4, nframes);
+    const dim3 g((P.H + 3) / 4, b.n);
     if (plan.iiw == 2)
-        k_ii_rowseg<128, 16><<<g, 256, 0, s>>>(frames, pitch, fstride, P.H, plan.rs_nstrips, plan.rs_rows, rowseg);
+        k_ii_rowseg<128, 16><<<g, 256, 0, s>>>(b.frames, b.pitch, b.stride, P.H, plan.rs_nstrips, plan.rs_rows, rowseg);
     else
-        k_ii_rowseg<hw::ST, hw::H><<<g, 256, 0, s>>>(frames, pitch, fstride, P.H, plan.rs_nstrips, plan.rs_rows,
+        k_ii_rowseg<hw::ST, hw::H><<<g, 256, 0, s>>>(b.frames, b.pitch, b.stride, P.H, plan.rs_nstrips, plan.rs_rows,
                                                      rowseg);
     return hipGetLastError();
 }
@@ -707,13 +706,11 @@ void make_plan(const FrameParams& P, const OctaveParams* oct, LaunchPlan& plan, 
     plan.q1_strips = P.noct > 1 ? (oct[1].sw + 63) / 64 : 0;
     const char* me = getenv("SURFHIP_Q01");
     plan.q01 = plan.q0 && plan.q1 && !(me && atoi(me) == 0);
-    // octave 0 on k_hess_p0 unless SURFHIP_P0=0; SURFHIP_P0=BG picks its
-    // barrier interval B (steps) and consumer waves G
-    // (value 10 B + G: barrier interval B steps, G consumer waves)
+    // octave 0 on k_hess_p0 unless SURFHIP_P0=0; SURFHIP_P0=BG (value 10 B + G)
+    // picks its barrier interval B (steps) and consumer waves G
     const char* pe = getenv("SURFHIP_P0");
     plan.p0 = (plan.q0 && !plan.q01) ? (pe ? atoi(pe) : 93) : 0;
-    if (plan.p0 != 0 && plan.p0 != 95 && plan.p0 != 94 && plan.p0 != 93 && plan.p0 != 92 && plan.p0 != 91 &&
-        plan.p0 != 32 && plan.p0 != 33)
+    if (plan.p0 != 0 && plan.p0 != 95 && plan.p0 != 93 && plan.p0 != 92 && plan.p0 != 91 && plan.p0 != 32)
         plan.p0 = 93;
     // the gather plan's octave 0 from LDS tiles (k_hessian_t0) when its
     // corners reach at most kT0Halo integral samples from the sample and the
@@ -912,83 +909,87 @@ __global__ __launch_bounds__(256) void k_hessian_t0(const int32_t* __restrict__ 
     }
 }
 
-hipError_t launch_hessian(const uint8_t* frames, int pitch, long long fstride, const int32_t* ii, float* resp,
-                          int nframes, const FrameParams& P, const OctaveParams* d_oct, const OctaveParams* h_oct,
-                          const LaunchPlan& plan, hipStream_t s, int parts, uint32_t* rowseg, int32_t* ii_out,
-                          uint32_t* psum)
+// (ahead of launch_hess_oct0: k_hess_w keeps its place ahead of k_hess_p0 in the code object)
+hipError_t launch_hess_w(const HessianArgs& a, hipStream_t s)
 {
-    const int nf8 = (nframes + 7) & ~7;
-    // parts: 1 = the kernels that read the u8 frames, 2 = those that read the
-    // integral image (the two may run on different streams)
-    // (4 / 8: only the octave-0 / only the k_hess_w launch of part 1)
-    const bool p0p = (parts & 5) != 0, wp = (parts & 9) != 0, iip = (parts & 2) != 0;
-    const bool u8p = p0p || wp;
-    if (u8p && !frames && (plan.q0 || plan.q1 || plan.hw_n > 0)) return hipErrorInvalidValue;
-    auto launch_w = [&]() {
-        if (plan.hw_n > 0) {
-            const dim3 g(nf8 * plan.hw_nstrips);
-            const OctaveParams& q3 = h_oct[plan.hw_n >= 3 ? 3 : 2];
-            const bool wr = plan.iiw == 1 && ii_out && rowseg;
+    const LaunchPlan& plan = *a.plan;
+    const FrameBatch& b = a.b;
+    if (!b.frames && plan_reads_frames(plan)) return hipErrorInvalidValue;
+    if (plan.hw_n == 0) return hipSuccess;
+    const dim3 g(((b.n + 7) & ~7) * plan.hw_nstrips);
+    const OctaveParams& q3 = a.h_oct[plan.hw_n >= 3 ? 3 : 2];
+    const bool wr = plan.iiw == 1 && a.ii_out && a.rowseg;
 #define HW_LAUNCH(NO, IIW)                                                                                       \
-    k_hess_w<NO, IIW><<<g, hw::THREADS, 0, s>>>(frames, pitch, fstride, resp, P, h_oct[1], h_oct[2], q3,          \
-                                                plan.hw_nstrips, nframes, plan.hw_nblk, rowseg, ii_out, plan.rs_rows)
-            if (plan.hw_n >= 3) {
-                if (wr) HW_LAUNCH(3, true);
-                else HW_LAUNCH(3, false);
-            } else {
-                if (wr) HW_LAUNCH(2, true);
-                else HW_LAUNCH(2, false);
-            }
+    k_hess_w<NO, IIW><<<g, hw::THREADS, 0, s>>>(b.frames, b.pitch, b.stride, a.resp, *a.P, a.h_oct[1], a.h_oct[2], \
+                                                q3, plan.hw_nstrips, b.n, plan.hw_nblk, a.rowseg, a.ii_out,      \
+                                                plan.rs_rows)
+    if (plan.hw_n >= 3) {
+        if (wr) HW_LAUNCH(3, true);
+        else HW_LAUNCH(3, false);
+    } else {
+        if (wr) HW_LAUNCH(2, true);
+        else HW_LAUNCH(2, false);
+    }
 #undef HW_LAUNCH
-        }
-    };
-    if (p0p) {
-        const int nb0 = 8 * (((nf8 / 8) * plan.q0_strips + q0::WAVES - 1) / q0::WAVES);
-        const int nb1 = 8 * (((nf8 / 8) * plan.q1_strips + q1::WAVES - 1) / q1::WAVES);
-        if (plan.q01) {
-            k_hess_q01<<<dim3(nb0 + nb1), q0::THREADS, 0, s>>>(frames, pitch, fstride, resp, P, h_oct[0], h_oct[1],
-                                                               plan.q0_strips, plan.q1_strips, nb0, nframes);
-        } else {
-            const dim3 gp(nf8 * plan.q0_strips);
-            const int pb = plan.p0 / 10, pg = plan.p0 % 10;      // interval, consumer waves
-            // (iiw 2, only with the default 93: this launch writes the integral)
-            const bool wr0 = plan.iiw == 2 && ii_out && rowseg;
+    return hipGetLastError();
+}
+
+hipError_t launch_hess_oct0(const HessianArgs& a, hipStream_t s)
+{
+    const LaunchPlan& plan = *a.plan;
+    const FrameParams& P = *a.P;
+    const FrameBatch& b = a.b;
+    if (!b.frames && plan_reads_frames(plan)) return hipErrorInvalidValue;
+    const int nf8 = (b.n + 7) & ~7;
+    const int nb0 = 8 * (((nf8 / 8) * plan.q0_strips + q0::WAVES - 1) / q0::WAVES);
+    const int nb1 = 8 * (((nf8 / 8) * plan.q1_strips + q1::WAVES - 1) / q1::WAVES);
+    if (plan.q01) {
+        k_hess_q01<<<dim3(nb0 + nb1), q0::THREADS, 0, s>>>(b.frames, b.pitch, b.stride, a.resp, P, a.h_oct[0],
+                                                           a.h_oct[1], plan.q0_strips, plan.q1_strips, nb0, b.n);
+        return hipGetLastError();
+    }
+    const dim3 gp(nf8 * plan.q0_strips);
+    const int pb = plan.p0 / 10, pg = plan.p0 % 10;      // interval, consumer waves
+    // (iiw 2, only with the default 93: this launch writes the integral)
+    const bool wr0 = plan.iiw == 2 && a.ii_out && a.rowseg;
 #define P0_CASE(BB, GG)                                                                                          \
     else if (pb == BB && pg == GG) k_hess_p0<BB, GG, SURF_P0_PLANE_NT, false><<<gp, 64 * (1 + GG), 0, s>>>(        \
-        frames, pitch, fstride, resp, P, h_oct[0], plan.q0_strips, nframes, nullptr, nullptr, 0, nullptr, 0);
-            // (rsum, only with the default 93 and k_hess_w writing the
-            // integral: this launch also leaves its strips' row sums in psum,
-            // k_rowsum_p0 adds them up into rowseg for the k_hess_w launch
-            // that follows on this stream)
-            const bool rs0 = plan.rsum && plan.iiw == 1 && ii_out && rowseg && psum;
-            if (wr0 && pb == 9 && pg == 3)
-                k_hess_p0<9, 3, SURF_P0_PLANE_NT, true><<<gp, 64 * 4, 0, s>>>(frames, pitch, fstride, resp, P, h_oct[0],
-                                                               plan.q0_strips, nframes, rowseg, ii_out, plan.rs_rows,
-                                                               nullptr, 0);
-            else if (rs0 && pb == 9 && pg == 3) {
-                k_hess_p0<9, 3, SURF_P0_PLANE_NT, false, true><<<gp, 64 * 4, 0, s>>>(
-                    frames, pitch, fstride, resp, P, h_oct[0], plan.q0_strips, nframes, nullptr, nullptr,
-                    plan.rs_rows, psum, plan.hw_nstrips);
-                k_rowsum_p0<hw::ST, hw::H><<<dim3((P.H + 255) / 256, nframes), 256, 0, s>>>(
-                    psum, P.H, plan.q0_strips, plan.rs_nstrips, plan.rs_rows, rowseg);
-            }
-            P0_CASE(9, 5) P0_CASE(9, 4) P0_CASE(9, 3) P0_CASE(9, 2) P0_CASE(9, 1) P0_CASE(3, 2) P0_CASE(3, 3)
-#undef P0_CASE
-            else if (plan.q0)
-                k_hess_q0<4, 1, 2><<<dim3(nb0), q0::THREADS, 0, s>>>(frames, pitch, fstride, resp, P, h_oct[0],
-                                                                     plan.q0_strips, nframes);
-            if (plan.q1)
-                k_hess_q1<2><<<dim3(nb1), q1::THREADS, 0, s>>>(frames, pitch, fstride, resp, P, h_oct[1],
-                                                               plan.q1_strips, nframes);
-        }
+        b.frames, b.pitch, b.stride, a.resp, P, a.h_oct[0], plan.q0_strips, b.n, nullptr, nullptr, 0, nullptr, 0);
+    // (rsum, only with the default 93 and k_hess_w writing the integral: this
+    // launch also leaves its strips' row sums in psum, k_rowsum_p0 adds them
+    // up into rowseg for the k_hess_w launch that follows on this stream)
+    const bool rs0 = plan.rsum && plan.iiw == 1 && a.ii_out && a.rowseg && a.psum;
+    if (wr0 && pb == 9 && pg == 3)
+        k_hess_p0<9, 3, SURF_P0_PLANE_NT, true><<<gp, 64 * 4, 0, s>>>(b.frames, b.pitch, b.stride, a.resp, P,
+                                                                      a.h_oct[0], plan.q0_strips, b.n, a.rowseg,
+                                                                      a.ii_out, plan.rs_rows, nullptr, 0);
+    else if (rs0 && pb == 9 && pg == 3) {
+        k_hess_p0<9, 3, SURF_P0_PLANE_NT, false, true><<<gp, 64 * 4, 0, s>>>(
+            b.frames, b.pitch, b.stride, a.resp, P, a.h_oct[0], plan.q0_strips, b.n, nullptr, nullptr, plan.rs_rows,
+            a.psum, plan.hw_nstrips);
+        k_rowsum_p0<hw::ST, hw::H><<<dim3((P.H + 255) / 256, b.n), 256, 0, s>>>(
+            a.psum, P.H, plan.q0_strips, plan.rs_nstrips, plan.rs_rows, a.rowseg);
     }
-    if (wp) launch_w();
-    if (plan.t0 && iip)
-        k_hessian_t0<kT0Halo><<<dim3(frame_grid(nframes) * plan.t0_nbx * plan.t0_nby), 256, 0, s>>>(
-            ii, resp, P, h_oct[0], plan.t0_nbx, plan.t0_nby, nframes);
-    if (plan.hess_start[kMaxOct] > 0 && iip)
-        k_hessian<<<dim3(frame_grid(nframes) * plan.hess_start[kMaxOct]), 256, 0, s>>>(ii, resp, P, d_oct, plan,
-                                                                                        nframes);
+    P0_CASE(9, 5) P0_CASE(9, 3) P0_CASE(9, 2) P0_CASE(9, 1) P0_CASE(3, 2)
+#undef P0_CASE
+    else if (plan.q0)
+        k_hess_q0<4, 1, 2><<<dim3(nb0), q0::THREADS, 0, s>>>(b.frames, b.pitch, b.stride, a.resp, P, a.h_oct[0],
+                                                             plan.q0_strips, b.n);
+    if (plan.q1)
+        k_hess_q1<2><<<dim3(nb1), q1::THREADS, 0, s>>>(b.frames, b.pitch, b.stride, a.resp, P, a.h_oct[1],
+                                                       plan.q1_strips, b.n);
+    return hipGetLastError();
+}
+
+hipError_t launch_hess_ii(const HessianArgs& a, hipStream_t s)
+{
+    const LaunchPlan& plan = *a.plan;
+    if (plan.t0)
+        k_hessian_t0<kT0Halo><<<dim3(frame_grid(a.b.n) * plan.t0_nbx * plan.t0_nby), 256, 0, s>>>(
+            a.ii, a.resp, *a.P, a.h_oct[0], plan.t0_nbx, plan.t0_nby, a.b.n);
+    if (plan.hess_start[kMaxOct] > 0)
+        k_hessian<<<dim3(frame_grid(a.b.n) * plan.hess_start[kMaxOct]), 256, 0, s>>>(a.ii, a.resp, *a.P, a.d_oct, plan,
+                                                                                     a.b.n);
     return hipGetLastError();
 }
 
@@ -1724,15 +1725,13 @@ __global__ __launch_bounds__(256) void k_nms_fit(const int32_t* __restrict__ ii,
 hipError_t launch_nms(const int32_t* ii, const float* resp, int nframes, const FrameParams& P,
                       const OctaveParams* d_oct, const LaunchPlan& plan, uint32_t* scan_key, uint32_t* scan_src,
                       float* scan_cube, int* item_count, int* item_off, surfhip_point* cand, uint32_t* keys,
-                      int* cand_count, int cap, int* status, hipStream_t s, bool stash_trace,
-                      const std::function<hipError_t()>* after_scan)
+                      int* cand_count, int cap, int* status, hipStream_t s, bool stash_trace)
 {
     const int per = plan.nms_start[kMaxOct];
     if (per == 0) {
         // (no NMS level: nothing to scan; the counters the sort reads are 0)
         hipError_t e = hipMemsetAsync(cand_count, 0, sizeof(int) * (size_t)nframes, s);
         if (e == hipSuccess) e = hipMemsetAsync(status, 0, sizeof(int), s);
-        if (e == hipSuccess && after_scan) e = (*after_scan)();
         return e;
     }
     // the scan's fit records for every batch size (round 5: one 1080p frame's
@@ -1744,10 +1743,6 @@ hipError_t launch_nms(const int32_t* ii, const float* resp, int nframes, const F
     auto* scan = cube ? &k_nms_scan<true> : &k_nms_scan<false>;
     scan<<<dim3(frame_grid(nframes) * per), 256, 0, s>>>(resp, P, d_oct, plan, scan_key, scan_src, scan_cube,
                                                                 item_count, nframes, cand_count, status);
-    if (after_scan) {
-        const hipError_t e = (*after_scan)();
-        if (e != hipSuccess) return e;
-    }
     const int nitems = nframes * per * 4;
     launch_excl_scan(item_count, nitems, item_off, item_off + nitems + 1, s);
     k_nms_fit<<<fit_grid(), 256, 0, s>>>(ii, resp, P, d_oct, scan_key, scan_src, scan_cube, item_off, nitems, per * 4,
