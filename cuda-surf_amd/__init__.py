@@ -60,7 +60,7 @@ STAGES = ("integral", "hessian", "nms", "sort", "describe", "total")
 # ------------------------------------------------------------------ library
 
 # SURFHIP_LIB_DIR: a directory holding an alternative build of libsurfhip.so
-# (diagnostic kernel variants, tools/diag_build.sh); the default is in-tree.
+# (another revision's, tools/build_rev.sh -> cuda-surf_amd/diag/<name>); the default is in-tree.
 LIB_PATH = os.path.join(os.environ.get("SURFHIP_LIB_DIR") or _HERE, "libsurfhip.so")
 SYNTH_PATH = os.path.join(_HERE, "libsurfsynth.so")
 

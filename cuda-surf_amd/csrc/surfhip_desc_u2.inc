@@ -32,22 +32,20 @@
 // float rounding of the summation order (<= 1e-6 relative, inside the 1e-4
 // tolerance); deterministic (no atomics, fixed orders).
 
-#ifndef SURF_U2_RING
-#define SURF_U2_RING 4
-#endif
-#ifndef SURF_U2_DMA_AUX
-#define SURF_U2_DMA_AUX 0              // the ring DMAs' cache-policy bits (A/B)
-#endif
-#ifndef SURF_U2_DMAMASK
-#define SURF_U2_DMAMASK 1              // lanes without data masked off, not sent out of bounds (0: the old form, A/B)
-#endif
 namespace du2 {
+constexpr int DMA_AUX = 0;                  // the ring DMAs' cache-policy bits
 // LDS-DMA ring slots: a step's DMA is issued RING - 2 steps before its rows
 // are read.  Measured (kernel trace, one box): 4 slots 2.52 ms, 6 slots 3.24,
 // 8 slots 3.33 -- the LDS of the deeper rings costs workgroups per CU (4 / 3
 // / 2) and the extra steps in flight do not buy it back.
-constexpr int RING = SURF_U2_RING;
+constexpr int RING = 4;
 static_assert(RING >= 4 && RING <= 8 && RING % 2 == 0, "ring: 4, 6 or 8 slots");
+// Widest span (16-B chunks) that takes the ring.  64: spans of 33-64 chunks
+// (grid steps >= 4) take it too, with 256-word slot rows, so only one row set
+// (single mode) fits a slot and they run single even when side <= 32.
+// Measured slower than the sparse path (describe 2.20-2.23 vs 2.08-2.11 ms,
+// profiles/r04l_*), hence 32
+constexpr int SEGW = 32;
 constexpr int SLOT = 128;                   // 16-B chunks per step: <= 2 x 64-lane DMA instructions
 constexpr int SLOTW = SLOT * 4;             // words per slot
 }  // namespace du2
@@ -100,15 +98,6 @@ __device__ __forceinline__ float du_pick(const v2f32 (&a)[NS / 2], int i)
         return (i >> 2) ? p.y : p.x;
     }
 }
-
-#ifdef SURF_DIAG_U2_STAMP
-// (diagnostic) per-wave s_memtime totals of the keypoint loop's phases and the
-// keypoints per row path (tools/u2_stamps.py): [wave][setup, rows seg, rows
-// sparse, rows generic, reduction, normalise+store, n seg, n sparse, n generic,
-// seg: ticks to the first ring wait's end, n narrow (W4 <= 16), narrow rows ticks]
-__device__ unsigned long long g_dstamp[8192][12];
-#define U2_T() __builtin_amdgcn_s_memtime()
-#endif
 
 template <bool EXT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXT ? 3 : 4))) void k_describe_u2(const int32_t* __restrict__ ii, FrameParams P,
@@ -186,11 +175,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXT ? 3 : 4
     // (the trace words stay in a VGPR, read at their use: SGPRs are full)
     float ptr = pv;
     float nrs = __int_as_float(entry(10));
-#ifdef SURF_DIAG_U2_STAMP
-    unsigned long long ph[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int path = 0;
-    unsigned long long ta = U2_T(), tb = 0, tc = 0, td = 0, tcold = 0;
-#endif
     while (gc < gend) {
         // the lane index again, opaque (volatile asm): every lane-derived
         // value is recomputed per keypoint instead of hoisted out of the
@@ -205,13 +189,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXT ? 3 : 4
         const int step = npk & 1023, hs = (npk >> 10) & 4095, iradius = npk >> 22;
         if (g1 < gend) pv = ld_w(g1);
         const int a2 = kq.issue(lane);
-#ifdef SURF_DIAG_U2_FRAME0
-        // (diagnostic: every keypoint reads frame 0's integral image -- the
-        // same windows and order, their misses served from the MALL)
-        const uint32_t* I = reinterpret_cast<const uint32_t*>(ii) + (size_t)(f & 0) * P.ii_stride;
-#else
         const uint32_t* I = reinterpret_cast<const uint32_t*>(ii) + (size_t)f * P.ii_stride;
-#endif
         const __amdgpu_buffer_rsrc_t rsrc = frame_rsrc(I, P.ii_stride * 4);
         const int rlim = P.iH - 1 - hs, clim = P.W - hs;
         const int side = 2 * iradius + 1;
@@ -243,16 +221,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXT ? 3 : 4
         // chunks from column cs
         const int cs = (ix + (-2 - iradius) * step) & ~3;
         const int W4 = (ix + (side + 1 - iradius) * step + 2 - cs + 3) >> 2;
-        // SURF_U2_SEGW=64: spans of 33-64 chunks (grid steps >= 4) take the
-        // LDS ring too, with 256-word slot rows, so only one row set (single
-        // mode) fits a slot and they run single even when side <= 32.
-        // Measured slower than the sparse path (describe 2.20-2.23 vs
-        // 2.08-2.11 ms, profiles/r04l_*): off by default
-#ifndef SURF_U2_SEGW
-#define SURF_U2_SEGW 32
-#endif
         const bool wide64 = W4 > 32;
-        const bool dual = side <= 32 && !(wide64 && W4 <= SURF_U2_SEGW);
+        const bool dual = side <= 32 && !(wide64 && W4 <= du2::SEGW);
         const int j = dual ? (lane & 31) : lane;
         const int h = dual ? (lane >> 5) : 0;
         const int sj = j - iradius;
@@ -324,10 +294,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXT ? 3 : 4
             wav2 = (int32_t)(vt - vb);
         };
         auto sample_hv = [&](auto AC, const DuHV& X, const DuHV& Y, const DuHV& Z, float rp, float4 wr, bool ok) {
-#ifdef SURF_DIAG_U2_NOSMP
-            acc[0][0].x += (float)(X.h0 ^ Y.v1 ^ Z.h1 ^ X.v0) + rp + wr.x;
-            return;
-#endif
             int32_t wav1, wav2;
             wavs(AC, X, Y, Z, wav1, wav2);
             add_sample(wav1, wav2, rp, wr, ok);
@@ -336,16 +302,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXT ? 3 : 4
         // or 128: W4 <= 16 or 32), so every read offset but the lane's own
         // column is a compile-time constant
         // (W4 <= 32: any step <= 3; W4 33..64: single mode, see above)
-        const bool seg = share && W4 <= SURF_U2_SEGW && (wide64 || step <= 3);
-#ifdef SURF_DIAG_U2_STAMP
-        tb = U2_T();
-        path = seg ? 1 : share ? 2 : 3;
-#endif
-#ifdef SURF_DIAG_U2_NOROWS
-        if (false) {
-#else
+        const bool seg = share && W4 <= du2::SEGW && (wide64 || step <= 3);
         if (seg) {
-#endif
             // ---- LDS-DMA ring.  Step s (grid rows t0 + pb + 2 s (+ 1 for
             // the second half)) lands in slot (s + 1) & 3 (four separate
             // arrays, see above): lane k of DMA instruction i loads chunk kk =
@@ -355,11 +313,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXT ? 3 : 4
             // past the span's chunks and lanes past 2 G rows load nothing (OOB).
             // The step loop is unrolled by the ring's 4 slots: no branches, 1-2
             // DMAs, 4 paired LDS reads and the rows' 2 table reads a step.
-#ifdef SURF_DIAG_U2_NOCONF
-            const int xo = j;                                 // (diagnostic: bank-conflict-free, wrong columns)
-#else
             const int xo = (j < side) ? c - cs : 2 * hs;      // the lane's column in the span
-#endif
             // (G, the row sets a step holds, is a template argument here: with
             // a run-time DMA count per step the compiler split every step into
             // blocks and moved the steps' arithmetic out of them)
@@ -391,25 +345,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXT ? 3 : 4
                     if (nmax == 0) continue;
                     const int dstep = 2 * step * ip4;           // bytes per step (two grid rows down)
                     const int o0 = ck[0] + (pb - 2) * step * ip4, o1 = ck[1] + (pb - 2) * step * ip4;
-#if SURF_U2_DMAMASK
                     const bool a0 = ck[0] != (int)kOOB, a1 = ck[1] != (int)kOOB;
-#endif
                     // step s's DMAs into slot (s + 1) & 3 (static SL)
                     auto dma = [&](auto SLC, int s) {
                         uint32_t* const slot = slots[decltype(SLC)::value];
                         const int d = (s + 1) * dstep;
-#if SURF_U2_DMAMASK
                         // lanes past the span's chunks are masked off, not sent
                         // out of bounds (lane 0 / 64 always load: no DMA is skipped,
                         // so the counted vmcnt waits hold)
-                        if (a0) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lv*)slot, 16, o0 + d, 0, 0, SURF_U2_DMA_AUX);
+                        if (a0) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lv*)slot, 16, o0 + d, 0, 0, du2::DMA_AUX);
                         if constexpr (nd == 2)
-                            if (a1) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lv*)(slot + 256), 16, o1 + d, 0, 0, SURF_U2_DMA_AUX);
-#else
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lv*)slot, 16, o0 + d, 0, 0, SURF_U2_DMA_AUX);
-                        if constexpr (nd == 2)
-                            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lv*)(slot + 256), 16, o1 + d, 0, 0, SURF_U2_DMA_AUX);
-#endif
+                            if (a1) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lv*)(slot + 256), 16, o1 + d, 0, 0, du2::DMA_AUX);
                     };
                     auto hv = [&](auto SLC) -> DuHV {
                         lu32* const b = (lu32*)slots[decltype(SLC)::value];
@@ -418,11 +364,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXT ? 3 : 4
                     };
                     auto wait_dma = [&]() {
                         // step n + 1's DMAs: the RING - 2 steps issued after them may be in flight
-#ifdef SURF_U2_INFLIGHT
-                        constexpr int IF = SURF_U2_INFLIGHT;        // (diagnostic: fewer steps in flight)
-#else
                         constexpr int IF = RING - 2;
-#endif
                         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(nd * IF) : "memory");
                     };
                     // the previous keypoint's reduction rows (and the previous
@@ -433,9 +375,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXT ? 3 : 4
                     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
                     static_for<RING>([&](auto IC) { dma(IntC<decltype(IC)::value>{}, decltype(IC)::value - 1); });
                     wait_dma();
-#ifdef SURF_DIAG_U2_STAMP
-                    if (ph == 0) tcold = U2_T();
-#endif
                     DuHV A = hv(IntC<0>{}), B = hv(IntC<1>{});
                     const int tb = t0 + hh;
                     // step n = n4 + U: DMA of step n + RING - 1 (slot U), table
@@ -474,12 +413,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXT ? 3 : 4
                         const uint32_t pre = Y.h1 - ht;
                         wait_dma();
                         XZ = hv(IntC<(U + 2) % RING>{});
-#ifdef SURF_DIAG_U2_NOSMP
-                        acc[0][0].x += (float)(pre ^ vt ^ XZ.h1 ^ XZ.v0) + wgt + wr.x;
-#else
                         const uint32_t hb = AM ? XZ.h1 : XZ.h0, vb = AM ? XZ.v1 : XZ.v0;
                         add_sample_w((int32_t)(pre - (hb - Y.h0)), (int32_t)(vt - vb), wgt, wr);
-#endif
                     };
                     // (the last round stops at nmax: steps past it hold no
                     // sample, and their DMAs feed no later read)
@@ -494,11 +429,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXT ? 3 : 4
                     }
                 }
             };
-#ifdef SURF_U2_FORCEWIDE
-            const bool narrow = false;
-#else
             const bool narrow = W4 <= 16;
-#endif
             auto rows_g = [&](auto AC, auto RSC) {
                 if constexpr (decltype(RSC)::value == 256) rows_dma(AC, RSC, IntC<1>{});
                 else if (dual) rows_dma(AC, RSC, IntC<2>{});
@@ -513,11 +444,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXT ? 3 : 4
             else rows_w(std::integral_constant<bool, false>());
             // the ring's last DMAs have landed before it holds the reduction
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#if defined(SURF_DIAG_U2_NOROWS) || defined(SURF_DIAG_U2_ONLYSEG)
-        } else if (false) {
-#else
         } else if (share) {
-#endif
             // ---- sparse rows (step > 3 or a wide span): per integral row a
             // lane loads its (c, c + 1) pair; columns c - s and c + s + 1 come
             // from lanes j -+ 2 (DPP wave shifts), the two edge lanes on each
@@ -533,7 +460,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXT ? 3 : 4
                 const int o = ld_on ? rb + oC : (int)kOOB;
                 const int oe = (ld_on && (eL || eR)) ? rb + oE : (int)kOOB;
                 Raw q;
-#if SURF_U2_DMAMASK
                 // loads only on the lanes that use them (the edge loads: <= 4
                 // lanes): masked-off lanes cost no address cycles, unlike
                 // out-of-bounds ones; their values are never read
@@ -549,12 +475,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXT ? 3 : 4
                     q.elo = bld(rsrc, oe);
                     q.ehi = bld(rsrc, oe + ip4);
                 }
-#else
-                q.lo = __builtin_amdgcn_raw_buffer_load_b64(rsrc, o, 0, 0);
-                q.hi = __builtin_amdgcn_raw_buffer_load_b64(rsrc, ld_on ? o + ip4 : (int)kOOB, 0, 0);
-                q.elo = bld(rsrc, oe);
-                q.ehi = bld(rsrc, (ld_on && (eL || eR)) ? oe + ip4 : (int)kOOB);
-#endif
                 return q;
             };
             auto rows = [&](auto AC) {
@@ -599,11 +519,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXT ? 3 : 4
             };
             if (hmode == 0) rows(std::integral_constant<bool, true>());
             else rows(std::integral_constant<bool, false>());
-#if defined(SURF_DIAG_U2_NOROWS) || defined(SURF_DIAG_U2_ONLYSEG)
-        } else if (false) {
-#else
         } else {
-#endif
             // ---- generic (s = 2 step + 1 at exact half-way scales): 12
             // gathers per sample
             const int oA = (c - hs) * 4, oB = (c + hs + 1) * 4, oC = c * 4;
@@ -623,9 +539,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXT ? 3 : 4
                 }
             }
         }
-#ifdef SURF_DIAG_U2_STAMP
-        tc = U2_T();
-#endif
         // ---- getTrace (surfd.cu:369-377, makePoint's laplace) when the fit
         // left it here (its inputs in the entry, nms_fit_point): lane l < 16
         // loads corner l & 3 of box l >> 2 -- the rows the window's DMAs just
@@ -737,14 +650,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXT ? 3 : 4
         float v[NB];
 #pragma unroll
         for (int b = 0; b < NB; b++) v[b] = 0.f;
-#ifdef SURF_DIAG_U2_NORED
-        (void)lo; (void)hi; (void)own;
-        {
-            const lf32* const rr = red_row(lane);
-#pragma unroll
-            for (int b = 0; b < NB; b++) v[b] = rr[oR * NB + b];
-        }
-#else
         for (int jj = lo + (qq & 1); jj < hi; jj += 2) {
             const lf32* const rr = red_row(jj);
             const float cf = rr[CFI];
@@ -758,16 +663,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXT ? 3 : 4
                 v[4 * q4 + 3] = __builtin_fmaf(x.w, wt, v[4 * q4 + 3]);
             }
         }
-#endif
         // quarters: (qq 0 + qq 1) + (qq 2 + qq 3) into lanes 0..15
 #pragma unroll
         for (int b = 0; b < NB; b++) {
             v[b] = du_tree_step<16>(v[b]);
             v[b] = du_tree_step<32>(v[b]);
         }
-#ifdef SURF_DIAG_U2_STAMP
-        td = U2_T();
-#endif
         // ---- normalize (surfd.cu:2447-2493): sum of squares over the 16
         // output lanes' NB values each
         float a = 0.f;
@@ -821,30 +722,5 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXT ? 3 : 4
                 *reinterpret_cast<float4*>(out + rc * NB + 4 * q4) =
                     make_float4(v[4 * q4] * fac, v[4 * q4 + 1] * fac, v[4 * q4 + 2] * fac, v[4 * q4 + 3] * fac);
         }
-#ifdef SURF_DIAG_U2_STAMP
-        {
-            const unsigned long long te = U2_T();
-            ph[0] += tb - ta;
-            ph[path] += tc - tb;
-            ph[4] += td - tc;
-            ph[5] += te - td;
-            ph[5 + path] += 1;
-            if (path == 1) {
-                ph[9] += tcold - tb;
-                if (W4 <= 16) { ph[10] += 1; ph[11] += tc - tb; }
-            }
-            ta = te;
-        }
-#endif
     }
-#ifdef SURF_DIAG_U2_STAMP
-    if ((threadIdx.x & 63) < 12) {
-        const int wg = blockIdx.x * 4 + (threadIdx.x >> 6);
-        unsigned long long v = 0;
-#pragma unroll
-        for (int i = 0; i < 12; i++)
-            if ((threadIdx.x & 63) == i) v = ph[i];
-        if (wg < 8192) g_dstamp[wg][threadIdx.x & 63] = v;
-    }
-#endif
 }

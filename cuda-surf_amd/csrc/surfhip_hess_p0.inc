@@ -31,11 +31,9 @@
 // exact integers), hence to the reference's int32 arithmetic.
 
 namespace p0 {
-#ifdef SURF_P0_PD
-constexpr int PD = SURF_P0_PD;
-#else
 constexpr int PD = 6;                     // producer: steps of u8 rows loaded ahead
-#endif
+constexpr int PLANE_NT = 1;               // octave-0 plane stores non-temporal (0: default policy)
+constexpr int IIW_AUX = 2;                // integral-image stores' cache policy (IIW): nt
 static_assert(q0::P % PD == 0, "prefetch slot static within an epoch");
 // (RS) the integral writer's strips whose row sums the producer prepares:
 // k_hess_w's, halo column X_k = XST k - XHALO (hw::ST, hw::H; checked where
@@ -43,20 +41,12 @@ static_assert(q0::P % PD == 0, "prefetch slot static within an epoch");
 constexpr int XST = 480, XHALO = 144;
 static_assert(XST % 4 == 0 && XHALO % 4 == 0, "every X on a lane boundary (4 columns per lane)");
 }  // namespace p0
-#ifndef SURF_P0_PLANE_NT
-#define SURF_P0_PLANE_NT 1         // octave-0 plane stores non-temporal (0: default policy, A/B)
-#endif
-#ifndef SURF_P0_IIW_AUX
-#define SURF_P0_IIW_AUX 2          // integral-image stores' cache policy (IIW): nt
-#endif
 
 // LDS ordering: every wave's LDS ops done, then the workgroup barrier (no
 // vmcnt wait: the producer's prefetch loads stay in flight)
 __device__ __forceinline__ void p0_barrier()
 {
-#ifndef SURF_DIAG_P0_NOBAR
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
 }
 
 // ---------------------------------------------------------------- producer
@@ -145,12 +135,8 @@ __device__ __forceinline__ void p0_producer(const uint8_t* __restrict__ frames, 
         const uint32_t ex = wave_incl_scan(tp) - tp;
         const uint32_t b0 = ex & 0xffffu, b1 = ex >> 16;
         if constexpr (IIW) {
-#ifdef SURF_DIAG_P0_IIW_NOST
-            // (diag) the accumulators without the stores
-#define P0_IIST(off) asm volatile("" ::"v"(G0), "v"(G1 & pm1), "v"(G2 & pm2), "v"(G3 & pm3), "s"(off))
-#else
 // (the row offset goes into the VGPR offset.  With it as the scalar offset
-// (SURF_DIAG_P0_IIW_SOFF, k < 0 rows at 0x40000000), 240 of a 256-frame
+// (round 5's form, k < 0 rows at 0x40000000), 240 of a 256-frame
 // batch's integrals -- every frame from 16 on -- had wrong values in rows
 // 11-90 (tools/ii_batch_check.py), which flipped Laplacian signs in config
 // #3's frame 127; with the VGPR offset none does.  Cause (round 6, DESIGN §4
@@ -160,16 +146,9 @@ __device__ __forceinline__ void p0_producer(const uint8_t* __restrict__ frames, 
 // gfx950 needs one, and the scheduler put the rewrite right behind 48 of
 // these 72 stores.  Any offset past the resource is dropped, as the u8 row
 // loads rely on)
-#ifdef SURF_DIAG_P0_IIW_SOFF
-// (diag) the row offset as soffset: the failing form, kept to reproduce it
-#define P0_IIST(off)                                                                                             \
-    __builtin_amdgcn_raw_buffer_store_b128(v4u32{G0, G1 & pm1, G2 & pm2, G3 & pm3}, IR, vst, (off), SURF_P0_IIW_AUX)
-#else
 #define P0_IIST(off)                                                                                             \
     __builtin_amdgcn_raw_buffer_store_b128(v4u32{G0, G1 & pm1, G2 & pm2, G3 & pm3}, IR, vst + (uint32_t)(off), 0, \
-                                           SURF_P0_IIW_AUX)
-#endif
-#endif
+                                           p0::IIW_AUX)
             P0_IIST(so);
             const uint32_t e0 = b0 + s0;
             G0 = G0 + e0;
@@ -208,7 +187,6 @@ __device__ __forceinline__ void p0_producer(const uint8_t* __restrict__ frames, 
         static_for<q0::P>([&](auto kc) {
             constexpr int K = decltype(kc)::value;
             const int k = kb + K;
-#ifndef SURF_DIAG_P0_NOPROD
             const uint32_t r0 = pf0[K % p0::PD], r1 = pf1[K % p0::PD];
             pf0[K % p0::PD] = ldrow(2 * (k + p0::PD));
             pf1[K % p0::PD] = ldrow(2 * (k + p0::PD) + 1);
@@ -268,9 +246,6 @@ __device__ __forceinline__ void p0_producer(const uint8_t* __restrict__ frames, 
                 typedef uint32_t __attribute__((address_space(3))) lds_u;
                 ((lds_u*)rsl)[lane] = (uint32_t)(db - da) | ((uint32_t)(dx - da) << 16);
             }
-#else
-            (void)k;
-#endif
             if constexpr (K % B == B - 1) p0_barrier();
         });
     }
@@ -332,10 +307,6 @@ __device__ __forceinline__ void p0_consumer(float* __restrict__ resp, const Fram
     const rsrc_t QR = make_rsrc(rsb, RSW ? (long long)P.H * 4 : 0);
     (void)QR; (void)rsl;
     p0_barrier();                       // the producer's first interval
-#ifdef SURF_DIAG_P0_NOCONS
-    for (int t = 0; t < niter * (q0::P / B); t++) p0_barrier();
-    return;
-#endif
     for (int it = 0; it < niter; it++) {
         static_for<q0::P>([&](auto kc) {
             constexpr int K = decltype(kc)::value;
@@ -437,15 +408,11 @@ __device__ __forceinline__ void p0_consumer(float* __restrict__ resp, const Fram
                 const v2f32 pp = dxx * dyy;
                 const v2f32 q2 = dxy * dxy;
                 const v2f32 hv = (rr2 * (pp - q2)) * nrm;
-#ifdef SURF_DIAG_P0_NOSTORE
-                asm volatile("" :: "v"(hv));
-#else
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(hv.x), RS[i0], colb[i0], (uint32_t)roff[i0],
                                                       NT ? 2 : 0);
                 if constexpr (i1 != i0)
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(hv.y), RS[i1], colb[i1],
                                                           (uint32_t)roff[i1], NT ? 2 : 0);
-#endif
             });
 #pragma unroll
             for (int i = 0; i < NSC; i++) roff[i] += sp4;
@@ -486,13 +453,6 @@ k_hess_p0(const uint8_t* __restrict__ frames, int pitch, long long fstride, floa
     constexpr int NB = 2 * B;
     __shared__ __attribute__((aligned(16))) uint32_t T[NB][4 * q0::NJ];   // [slot][plane][NJ] float2
     __shared__ __attribute__((aligned(16))) uint32_t TD[2 * q0::NJ];      // Delta: [plane][NJ] float
-#ifdef SURF_DIAG_P0_EXTRA_LDS
-    // (diagnostic) LDS a fused octave-0 NMS ring would add (bytes): the
-    // occupancy it costs, with the work unchanged (DESIGN §6 item 24)
-    __shared__ uint32_t xlds[SURF_DIAG_P0_EXTRA_LDS / 4];
-    if (threadIdx.x == 0 && nframes < 0) xlds[blockIdx.x & 15] = 1u;
-    asm volatile("" ::"v"(xlds[threadIdx.x & 15]));
-#endif
     // (RS) an epoch's row sums on their way from the producer to the wave that stores them
     uint32_t* rsl = nullptr;
     if constexpr (RS) {

@@ -46,16 +46,10 @@
 // U = 20 blocks = the ring length); octaves 2 / 3 (a sample row every 2 / 4
 // blocks) shift their rings by one slot per sample row instead.
 
-#ifndef SURF_HW1_AUX
-#define SURF_HW1_AUX 0             // octave-1 response stores' cache policy (2: nt)
-#endif
-#ifndef SURF_HW_FAR_AUX
-#define SURF_HW_FAR_AUX 2          // octave-2/3 response stores' cache policy (2: nt)
-#endif
-#ifndef SURF_HW_IIW_AUX
-#define SURF_HW_IIW_AUX 2          // integral-image stores' cache policy (IIW): nt (0: default, A/B)
-#endif
 namespace hw {
+constexpr int OCT1_AUX = 0;        // octave-1 response stores' cache policy (2: nt)
+constexpr int FAR_AUX = 2;         // octave-2/3 response stores' cache policy (2: nt)
+constexpr int IIW_AUX = 2;         // integral-image stores' cache policy (IIW): nt (0: default)
 constexpr int ST = 480;            // image columns per strip (30 octave-3 samples)
 constexpr int H = 144;             // halo: octave 3's reach (3 x 47 + 2 = 143)
 constexpr int NP = 3;              // producer waves, 256 local-integral columns each
@@ -67,11 +61,7 @@ constexpr int BLKB = ENT * 16;     // bytes per block
 constexpr int BSTR = NLB * BLKB;   // block b of every interval buffer lies at b x BSTR: [BPI][NLB][ENT]
 constexpr int LAG = 4;             // consumers work on interval t - LAG in interval t
 constexpr int U = 20;              // blocks per octave-1 iteration (= its ring length)
-#ifdef SURF_HW_PD
-constexpr int PD = SURF_HW_PD;
-#else
 constexpr int PD = 1;              // producer: intervals of u8 rows loaded ahead
-#endif
 constexpr int WAVES = NP + 6 + 3 + 3;
 constexpr int THREADS = 64 * WAVES;
 static_assert(U % BPI == 0 && (U / BPI) % NLB == 0, "static buffer index in the octave-1 loop");
@@ -116,32 +106,10 @@ __host__ __device__ constexpr int cof(int K, int i)
 // LDS ordering: every wave's LDS writes done, then the workgroup barrier.
 // Not __syncthreads(): its release fence would also wait for the producers'
 // global prefetch loads (vmcnt(0)) at every block.
-#ifdef SURF_DIAG_W_STAMP
-// (diagnostic) every wave of workgroup SURF_DIAG_W_STAMP records s_memtime
-// before and after each of its barriers: which wave arrives last, and how
-// long the others wait (tools/w_stamps.py)
-constexpr int kWStampN = 400;
-__device__ unsigned long long g_wstamp[16][kWStampN][2];
-__device__ __forceinline__ void hw_barrier(int& bk)
-{
-    const bool me = blockIdx.x == SURF_DIAG_W_STAMP && (threadIdx.x & 63) == 0;
-    unsigned long long t0 = __builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    unsigned long long t1 = __builtin_amdgcn_s_memtime();
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (me && bk < kWStampN) {
-        volatile unsigned long long* d = &g_wstamp[w][bk][0];
-        d[0] = t0 + (threadIdx.x & 63);          // (lane-dependent: a vector store)
-        d[1] = t1 + (threadIdx.x & 63);
-    }
-    bk++;
-}
-#else
-__device__ __forceinline__ void hw_barrier(int&)
+__device__ __forceinline__ void hw_barrier()
 {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
-#endif
 
 __device__ __forceinline__ uint32_t opqu(uint32_t x)
 {
@@ -243,12 +211,6 @@ __device__ __forceinline__ void hw_producer(const uint8_t* __restrict__ frames, 
                                             const FrameParams& P, int f, int X0, int nint, uint32_t lds0,
                                             uint32_t* cbuf, const uint32_t* sg, int32_t* iib, bool last, int rs_rows)
 {
-#ifdef SURF_HW_PRODPRIO
-    // (A/B) the producers are the last to reach most barriers (barrier
-    // stamps): raise their issue priority over the consumers
-    __builtin_amdgcn_s_setprio(SURF_HW_PRODPRIO);
-#endif
-    int bk = 0;                                               // barriers passed (SURF_DIAG_W_STAMP)
     constexpr int NR = 4 * hw::BPI;                          // rows per interval
     const int lane = (int)lane_id();
     const int Hh = P.H;
@@ -306,7 +268,7 @@ __device__ __forceinline__ void hw_producer(const uint8_t* __restrict__ frames, 
         for (int j = 0; j < NR; j++) pf[K][j] = ldrow(NR * K + j);
     });
     // interval t = d + PW works on interval-block d; PW idle intervals first
-    static_for<PW>([&](auto) { hw_barrier(bk); });
+    static_for<PW>([&](auto) { hw_barrier(); });
     uint32_t bufoff = 0u;                                    // (d mod NLB) x BLKB
     for (int d0 = 0; d0 < nint; d0 += hw::PD + 1) {
         static_for<hw::PD + 1>([&](auto kc) {
@@ -370,18 +332,13 @@ __device__ __forceinline__ void hw_producer(const uint8_t* __restrict__ frames, 
                         // resource's iH ip4 bytes and are dropped by the range
                         // check, which sees the VGPR offset (§4 "Buffer range
                         // check"; non-owned lanes: 2^30 + R ip4 < 2^32)
-#ifdef SURF_DIAG_HW_IIW_SOFF
-                        // (diag) round 5's form: the row offset as the scalar offset
-                        const uint32_t ro = vst, so = (uint32_t)((NR * d + 4 * b + r) * ip4);
-#else
                         const uint32_t ro = vst + (uint32_t)((NR * d + 4 * b + r) * ip4), so = 0u;
-#endif
                         if constexpr (BND)
                             __builtin_amdgcn_raw_buffer_store_b128(v4u32{Lc[0], Lc[1] & pm[1], Lc[2] & pm[2],
-                                                                         Lc[3] & pm[3]}, IR, ro, so, SURF_HW_IIW_AUX);
+                                                                         Lc[3] & pm[3]}, IR, ro, so, hw::IIW_AUX);
                         else
                             __builtin_amdgcn_raw_buffer_store_b128(v4u32{Lc[0], Lc[1], Lc[2], Lc[3]}, IR, ro, so,
-                                                                   SURF_HW_IIW_AUX);
+                                                                   hw::IIW_AUX);
                     }
                     Lc[0] = Lc[0] + e;
                     Lc[1] = __builtin_amdgcn_udot4(p, 0x00000001u, Lc[1] + e, false);
@@ -408,11 +365,11 @@ __device__ __forceinline__ void hw_producer(const uint8_t* __restrict__ frames, 
                 }
             }
             bufoff = bufoff + hw::BLKB == hw::BSTR ? 0u : bufoff + hw::BLKB;
-            hw_barrier(bk);
+            hw_barrier();
         });
     }
     // trailing intervals: LAG + nint barriers in all
-    static_for<hw::LAG - PW>([&](auto) { hw_barrier(bk); });
+    static_for<hw::LAG - PW>([&](auto) { hw_barrier(); });
 }
 
 // an empty volatile asm that takes and "redefines" the column entries of term
@@ -435,7 +392,6 @@ template <int K>
 __device__ __forceinline__ void hw_oct1(float* __restrict__ resp, const FrameParams& P, const OctaveParams& q,
                                         int s, int f, int X0, int h, int nblk, uint32_t lds0)
 {
-    int bk = 0;                                               // barriers passed (SURF_DIAG_W_STAMP)
     constexpr int D = 4, U = hw::U;
     const int lane = (int)lane_id();
     const int ixl = 2 * lane + h;                             // sample column within the strip
@@ -458,10 +414,9 @@ __device__ __forceinline__ void hw_oct1(float* __restrict__ resp, const FramePar
     uint32_t nx[U], ny[U], nz[U];
 #pragma unroll
     for (int i = 0; i < U; i++) nx[i] = ny[i] = nz[i] = 0u;
-    static_for<hw::LAG>([&](auto) { hw_barrier(bk); });
+    static_for<hw::LAG>([&](auto) { hw_barrier(); });
     constexpr int FIN = hw::fdiv(3 * K + 2, D);              // block bc finalises sample row bc - FIN
     int roff = (-FIN - st.b1) * st.sp4;
-#ifndef SURF_HW1_SERIAL
     // Software pipeline over the term types (F, E, G) of consecutive blocks:
     // a type's column entries are read while the previous type's terms are
     // added, and the next block's F entries while this block's G terms are
@@ -519,54 +474,16 @@ __device__ __forceinline__ void hw_oct1(float* __restrict__ resp, const FramePar
             terms(jc, T2{}, QG);
             constexpr int fs = hw::fmodp(J - FIN, U);
             const float hv = hw_final(nx[fs], ny[fs], nz[fs], norm);
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(hv), st.R, st.colb, (uint32_t)roff, SURF_HW1_AUX);
-            roff += st.sp4;
-            if constexpr (J % hw::BPI == hw::BPI - 1) hw_barrier(bk);
-        });
-    }
-#else
-    for (int b0 = 0; b0 < nblk; b0 += U) {
-        static_for<U>([&](auto jc) {
-            constexpr int J = decltype(jc)::value;
-            constexpr int IB = (J / hw::BPI) % hw::NLB;
-            constexpr uint32_t BO = (uint32_t)(IB * hw::BLKB);
-            static_assert(BO < 65536u, "ds_read immediate offset");
-            // one term type at a time (F, E, G): at most 4 column entries (16
-            // registers) in flight, one block at a time
-            static_for<3>([&](auto tc) {
-                constexpr int T = decltype(tc)::value;
-#ifndef SURF_HW1_NOSB
-                __builtin_amdgcn_sched_barrier(0);
-#endif
-                v4u32 Q[10];
-#pragma unroll
-                for (int i = 0; i < 10; i++)
-                    Q[i] = hw_needs(T, i) ? hw_ld((J % hw::BPI == 0 ? ad[i] : ad2[i]) + BO) : v4u32{0u, 0u, 0u, 0u};
-                static_for<10>([&](auto nc) {
-                    constexpr int n = decltype(nc)::value;
-                    if constexpr (hw::ty(n) == T) {
-                        constexpr int R = hw::ro(K, n), j = hw::fmodp(R, D), sl = hw::fmodp(J - hw::fdiv(R, D), U);
-                        constexpr int C = hw::co(n);
-                        const uint32_t v = hw_term<T, j>(Q);
-                        if constexpr (T == 0) nx[sl] = hw_acc<C>(nx[sl], v);
-                        else if constexpr (T == 1) ny[sl] = hw_acc<C>(ny[sl], v);
-                        else nz[sl] = hw_acc<C>(nz[sl], v);
-                    }
-                });
-            });
-            constexpr int fs = hw::fmodp(J - FIN, U);
-            const float hv = hw_final(nx[fs], ny[fs], nz[fs], norm);
             // default cache policy, not nt: the two waves of a scale store
             // alternate columns of the same row within a block of each
             // other, and L2 merges the halves into whole lines (as nt
             // stores, each half went to HBM on its own: 1.57x the plane
             // bytes written, profiles/r03g_pmc.csv)
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(hv), st.R, st.colb, (uint32_t)roff, SURF_HW1_AUX);
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(hv), st.R, st.colb, (uint32_t)roff, hw::OCT1_AUX);
             roff += st.sp4;
-            if constexpr (J % hw::BPI == hw::BPI - 1) hw_barrier(bk);
+            if constexpr (J % hw::BPI == hw::BPI - 1) hw_barrier();
         });
     }
-#endif
 }
 
 // ---------------------------------------------------- octave 2 / 3 consumer
@@ -582,13 +499,8 @@ template <int D, int K>
 __device__ __forceinline__ void hw_far(float* __restrict__ resp, const FrameParams& P, const OctaveParams& q, int s,
                                        int f, int X0, int nblk, uint32_t lds0)
 {
-    int bk = 0;                                               // barriers passed (SURF_DIAG_W_STAMP)
     constexpr int PER = D / 4;
-#ifdef SURF_HW_FAR_KU
-    constexpr int KU = SURF_HW_FAR_KU;                     // (A/B: 1 = shift every period)
-#else
     constexpr int KU = 5;
-#endif
     static_assert((hw::U / PER) % KU == 0, "unrolled periods divide nblk / PER (nblk: a multiple of hw::U)");
     constexpr int DFIN = -hw::fdiv(3 * K + 2, D), DMAX = -hw::fdiv(-3 * K - 1, D);
     constexpr int NR = DMAX - DFIN + 1;
@@ -605,7 +517,7 @@ __device__ __forceinline__ void hw_far(float* __restrict__ resp, const FramePara
     uint32_t nx[NRR], ny[NRR], nz[NRR];
 #pragma unroll
     for (int i = 0; i < NRR; i++) nx[i] = ny[i] = nz[i] = 0u;
-    static_for<hw::LAG>([&](auto) { hw_barrier(bk); });
+    static_for<hw::LAG>([&](auto) { hw_barrier(); });
     constexpr int QF = hw::fmodp(3 * K + 2, D) / 4;         // block of the period that finalises ring slot 0
     int roff = (DFIN - st.b1) * st.sp4;                       // period m finalises sample row m + DFIN
     uint32_t bufoff = 0u;
@@ -653,12 +565,12 @@ __device__ __forceinline__ void hw_far(float* __restrict__ resp, const FramePara
                 });
                 if constexpr (QB == QF) {
                     const float hv = hw_final(nx[M], ny[M], nz[M], norm);
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(hv), st.R, st.colb, (uint32_t)roff, SURF_HW_FAR_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(hv), st.R, st.colb, (uint32_t)roff, hw::FAR_AUX);
                     roff += st.sp4;
                 }
                 if constexpr (QB % hw::BPI == hw::BPI - 1) {
                     bufoff = bufoff + hw::BLKB == hw::BSTR ? 0u : bufoff + hw::BLKB;
-                    hw_barrier(bk);
+                    hw_barrier();
                 }
             });
         });
@@ -721,8 +633,7 @@ __global__ __launch_bounds__(hw::THREADS) void k_hess_w(const uint8_t* __restric
                 else if (w == 13) hw_far<16, hw::kof(3, 1)>(resp, P, o3, 1, f, X0, nblk, l0);
                 else hw_far<16, hw::kof(3, 2)>(resp, P, o3, 2, f, X0, nblk, l0);
             } else {
-                int bk = 0;
-                for (int t = 0; t < hw::LAG + nblk / hw::BPI; t++) hw_barrier(bk);
+                for (int t = 0; t < hw::LAG + nblk / hw::BPI; t++) hw_barrier();
             }
             break;
     }

@@ -1039,7 +1039,7 @@ void or_match(or_point* pts1, const or_point* pts2, const float* f1, const float
 }
 
 /* Checker for the HIP kernels' descriptor-position quotient (div_by in
- * surfhip_kernels.hip: q0 = x r, q = fma(fma(-q0, y, x), r, q0) with r =
+ * surfhip_desc.inc: q0 = x r, q = fma(fma(-q0, y, x), r, q0) with r =
  * 1 / y): counts, over n pseudo-random (x, y) in the ranges the descriptor
  * kernels see (y = 3 * (1.65 * scale), scale in [1, 80); |x| < 400, or any
  * normal |x| >= 2^-100 against y of every exponent 2^1 .. 2^8 with random or

@@ -695,7 +695,7 @@ def test_descriptors_unit_norm_every_window(orc, wsz, extend):
 
 def test_descriptor_quotient_matches_ieee_division(orc):
     """The descriptor kernels compute rpos / cpos as x * r + fma remainder
-    correction (r = 1 / spacing once per keypoint, surfhip_kernels.hip
+    correction (r = 1 / spacing once per keypoint, surfhip_desc.inc
     div_by) instead of the reference's per-sample division (surfd.cu:1290-1292,
     2420-2430): the quotient must be the IEEE one, since rpos^2 + cpos^2
     indexes the Gaussian LUT."""

@@ -4,8 +4,8 @@
 # gpurun_out/ab_<tag>_<variant>_<round>.json and a summary line per run:
 # value, ms/step, the Hessian stage (in-step events and serial), describe.
 #   bash tools/ab.sh <tag> "<variant> <variant> ..." [pairs] [bench args...]
-# variant: "default" (cuda-surf_amd/) or a diag build name (cuda-surf_amd/diag/<name>,
-# tools/diag_build.sh); an "env:NAME=VAL[,NAME=VAL]" variant runs the default build with that env.
+# variant: "default" (cuda-surf_amd/) or the name of a variant library (cuda-surf_amd/diag/<name>,
+# built from a git revision by tools/build_rev.sh); an "env:NAME=VAL[,NAME=VAL]" variant runs the default build with that env.
 set -u
 TAG=$1; VARS=$2; PAIRS=${3:-2}; shift 3 2>/dev/null || shift $#
 cd /tmp && export TMPDIR=/tmp

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """SHA-256 of one batch's keypoints and descriptors (A/B of two builds of
 libsurfhip.so that must agree bit for bit: run once per SURFHIP_LIB_DIR and
-compare the lines).
+compare the lines).  tools/build_rev.sh <rev> <name> builds a revision's
+library into cuda-surf_amd/diag/<name>.
 
     SURFHIP_LIB_DIR=cuda-surf_amd/diag/<name> python3 tools/desc_hash.py [--config5]
 """

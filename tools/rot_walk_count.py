@@ -6,7 +6,7 @@ redundant: each of a wave's 50 cell lanes (25 floor cells x 2 row parities)
 walks the inverse-rotated box of its cell row by row, over the sj interval
 where the cell's two slabs cross the row (widened by kSlack), and rejects
 samples that are not its own by the exact membership test -- the model here
-restates that loop (surfhip_kernels.hip, k_describe_rot: grid box, row_range,
+restates that loop (surfhip_desc.inc, k_describe_rot: grid box, row_range,
 membership and border tests) in float32 numpy for the keypoints the oracle
 finds on synthetic 4K frames, and reports per keypoint:
 
