@@ -121,6 +121,8 @@ _sigs = {
     "surfhip_run_hessian": (_i, [_vp, _i]),
     "surfhip_hessian_bytes_per_frame": (C.c_longlong, [_vp]),
     "surfhip_hessian_plan": (C.c_int, [_vp, C.c_char_p, C.c_int]),
+    "surfhip_switches_from_env": (C.c_int, [C.c_char_p, C.c_int]),
+    "surfhip_detector_switches": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "surfhip_slab_bytes": (_sz, [_i, _i, _i]),
     "surfhip_batch_total": (_i, [_vp, _i, C.POINTER(_i)]),
     "surfhip_pack_slab": (_i, [_vp, _vp, _vp, _vp, _i, _vp]),
@@ -144,6 +146,9 @@ _sigs = {
     "surfhip_stream_bytes": (_sz, [_i, _sz]),
 }
 for _name, (_res, _args) in _sigs.items():
+    # (an earlier revision's build under SURFHIP_LIB_DIR may lack a newer export: calling it raises)
+    if os.environ.get("SURFHIP_LIB_DIR") and not hasattr(_lib, _name):
+        continue
     _f = getattr(_lib, _name)
     _f.restype = _res
     _f.argtypes = _args
@@ -175,6 +180,24 @@ def check(rc: int, what: str = "") -> None:
 
 def build_info() -> str:
     return _lib.surfhip_build_info().decode()
+
+
+def _text(fn, what: str) -> str:
+    """A text export (buf, len) -> full length: called again with room for all of it when cut."""
+    buf = C.create_string_buffer(256)
+    n = fn(buf, len(buf))
+    if n < 0:
+        check(n, what)
+    if n >= len(buf):
+        buf = C.create_string_buffer(n + 1)
+        check(min(0, fn(buf, len(buf))), what)
+    return buf.value.decode()
+
+
+def switches_from_env() -> str:
+    """The SURFHIP_* switches a detector created now would take, as "NAME=value ..." of the
+    variables that are set (surfhip_switches_from_env); needs no GPU."""
+    return _text(_lib.surfhip_switches_from_env, "switches_from_env")
 
 
 def align_up(a: int, b: int) -> int:
@@ -408,14 +431,11 @@ class Detector:
 
     def hessian_kernels(self) -> str:
         """The Hessian stage's kernels of this detector's plan (surfhip_hessian_plan)."""
-        buf = C.create_string_buffer(256)
-        n = _lib.surfhip_hessian_plan(self.h, buf, len(buf))
-        if n < 0:
-            check(n, "hessian_plan")
-        if n >= len(buf):                     # the plan text was cut: ask again with room for all of it
-            buf = C.create_string_buffer(n + 1)
-            check(min(0, _lib.surfhip_hessian_plan(self.h, buf, len(buf))), "hessian_plan")
-        return buf.value.decode()
+        return _text(lambda buf, n: _lib.surfhip_hessian_plan(self.h, buf, n), "hessian_plan")
+
+    def switches(self) -> str:
+        """The SURFHIP_* switches this detector read when it was created (surfhip_detector_switches)."""
+        return _text(lambda buf, n: _lib.surfhip_detector_switches(self.h, buf, n), "detector_switches")
 
     def slab_bytes(self, nframes: int, total: int, desc: bool = True) -> int:
         return int(_lib.surfhip_slab_bytes(nframes, total, self.nfeatures if desc else 0))

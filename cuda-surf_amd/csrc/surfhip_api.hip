@@ -55,6 +55,7 @@ struct surfhip_detector {
     int cus = 256;                      // compute units of dev (the describe kernels' persistent grid)
     hipStream_t stream = nullptr;
     surfhip_param param{};
+    Switches sw;                        // the SURFHIP_* switches as they were when the detector was created
     FrameParams P{};
     OctaveParams oct[kMaxOct]{};
     OctaveParams* d_oct = nullptr;      // device copy read by the fused launches
@@ -65,7 +66,7 @@ struct surfhip_detector {
     uint8_t* dbl = nullptr;             // doubled: the (2 srcW - 2) x (2 srcH - 2) frames D
     int dpitch = 0;
     long long dstride = 0;
-    int nbands = 0, CW = 0;
+    int CW = 0;
     size_t tot_osize = 0;
     int32_t* ii = nullptr;              // integral of the last processed batch (one of iib)
     int32_t* iib[2] = {nullptr, nullptr};   // integral buffers: the batch's, and the next batch's prefetch
@@ -105,7 +106,6 @@ struct surfhip_detector {
     hipEvent_t ev[SURFHIP_NSTAGE]{};
     hipStream_t side = nullptr;         // integral + integral-image Hessian kernels, beside the u8 ones
     hipEvent_t fork = nullptr, join = nullptr;
-    float stage_ms[SURFHIP_NSTAGE]{};
     bool time_hess = false;             // in-step Hessian event pairs (surfhip_detector_time_hessian)
     // per timed batch: [0] on the detector stream before the Hessian's fork,
     // [1] on it after the u8 kernels, [2] on the side stream after the
@@ -117,6 +117,85 @@ struct surfhip_detector {
     FrameBatch last;                    // u8 source of the last integral (surfhip_run_hessian)
     long long hess_bytes = 0;
 };
+
+// t into buf[len], cut to fit and NUL-terminated; returns the full length
+static int text_out(const std::string& t, char* buf, int len)
+{
+    if (buf && len > 0) {
+        const size_t n = std::min((size_t)len - 1, t.size());
+        memcpy(buf, t.data(), n);
+        buf[n] = 0;
+    }
+    return (int)t.size();
+}
+
+// The switches in the order of Switches' fields (bit i of Switches::set), and their names
+enum {
+    kSwHessGather, kSwHessW, kSwQ01, kSwP0, kSwHessT0, kSwIIFuse, kSwRowsum, kSwDescUr, kSwTraceDesc, kSwRotAtomic,
+    kSwSortBitonic, kSwPrefetch, kSwDescBeside, kSwU2LdsPad, kSwFitGrid, kSwFitCube, kSwIIBand, kSwIIBandSmall,
+    kSwitches
+};
+static const char* const kSwitchNames[kSwitches] = {
+    "SURFHIP_HESS_GATHER", "SURFHIP_HESS_W",      "SURFHIP_Q01",        "SURFHIP_P0",         "SURFHIP_HESS_T0",
+    "SURFHIP_II_FUSE",     "SURFHIP_ROWSUM",      "SURFHIP_DESC_UR",    "SURFHIP_TRACE_DESC", "SURFHIP_ROT_ATOMIC",
+    "SURFHIP_SORT_BITONIC", "SURFHIP_PREFETCH",   "SURFHIP_DESC_BESIDE", "SURFHIP_U2_LDSPAD", "SURFHIP_FIT_GRID",
+    "SURFHIP_FIT_CUBE",    "SURFHIP_II_BAND",     "SURFHIP_II_BAND_SMALL"};
+
+namespace surfhip {
+
+Switches read_switches()
+{
+    Switches w;
+    const char* v[kSwitches];
+    for (int i = 0; i < kSwitches; i++)
+        if ((v[i] = getenv(kSwitchNames[i])) != nullptr) w.set |= 1u << i;
+    auto num = [&](int i, int dflt) { return v[i] ? atoi(v[i]) : dflt; };
+    auto is = [&](int i, const char* text) { return v[i] && !strcmp(v[i], text); };
+    if (v[kSwHessGather]) w.hess_gather = atoi(v[kSwHessGather]) != 0;
+    w.hess_w = num(kSwHessW, w.hess_w) != 0;
+    w.q01 = num(kSwQ01, w.q01) != 0;
+    w.p0 = num(kSwP0, w.p0);
+    if (w.p0 != 0 && w.p0 != 95 && w.p0 != 93 && w.p0 != 92 && w.p0 != 91 && w.p0 != 32) w.p0 = 93;
+    w.hess_t0 = num(kSwHessT0, w.hess_t0) != 0;
+    const int fuse = num(kSwIIFuse, w.ii_fuse);
+    w.ii_fuse = fuse == 0 || fuse == 2 ? fuse : 1;
+    w.rowsum_rowseg = is(kSwRowsum, "rowseg");
+    if (v[kSwDescUr]) w.desc_ur = atoi(v[kSwDescUr]) != 0;
+    w.trace_desc = num(kSwTraceDesc, w.trace_desc) != 0;
+    w.rot_atomic = v[kSwRotAtomic] != nullptr;
+    w.sort_bitonic = v[kSwSortBitonic] != nullptr;
+    if (v[kSwPrefetch]) w.prefetch = is(kSwPrefetch, "describe");
+    w.desc_beside = num(kSwDescBeside, w.desc_beside);
+    w.u2_ldspad = num(kSwU2LdsPad, w.u2_ldspad);
+    if (v[kSwFitGrid]) w.fit_grid = std::max(64, atoi(v[kSwFitGrid]));
+    w.fit_cube = num(kSwFitCube, w.fit_cube) != 0;
+    // a band height out of range counts as unset
+    auto band = [&](int i, int lo, int hi, int& rows) {
+        const int b = num(i, rows);
+        if (b >= lo && b <= hi) rows = b;
+        else w.set &= ~(1u << i);
+    };
+    band(kSwIIBand, 8, 64, w.ii_band);
+    band(kSwIIBandSmall, 4, 32, w.ii_band_small);
+    return w;
+}
+
+std::string switches_text(const Switches& w)
+{
+    const std::string val[kSwitches] = {
+        std::to_string(w.hess_gather), std::to_string(w.hess_w),      std::to_string(w.q01),
+        std::to_string(w.p0),          std::to_string(w.hess_t0),     std::to_string(w.ii_fuse),
+        w.rowsum_rowseg ? "rowseg" : "p0", std::to_string(w.desc_ur), std::to_string(w.trace_desc),
+        std::to_string(w.rot_atomic),  std::to_string(w.sort_bitonic), w.prefetch == 1 ? "describe" : "nms",
+        std::to_string(w.desc_beside), std::to_string(w.u2_ldspad),   std::to_string(w.fit_grid),
+        std::to_string(w.fit_cube),    std::to_string(w.ii_band),     std::to_string(w.ii_band_small)};
+    std::string t;
+    for (int i = 0; i < kSwitches; i++)
+        if (w.set >> i & 1) t += (t.empty() ? "" : " ") + std::string(kSwitchNames[i]) + "=" + val[i];
+    return t;
+}
+
+}  // namespace surfhip
 
 extern "C" {
 
@@ -457,6 +536,7 @@ int surfhip_detector_create(surfhip_detector** out, const surfhip_param* param, 
                                 param->extend, param->desc_wsz);
     if (rc != SURFHIP_OK) return rc;
     surfhip_detector* d = new surfhip_detector();
+    d->sw = read_switches();
     d->param = chk;
     d->srcW = width;
     d->srcH = height;
@@ -492,7 +572,6 @@ int surfhip_detector_create(surfhip_detector** out, const surfhip_param* param, 
         delete d;
         return rc;
     }
-    d->nbands = (d->H + big_band_rows() - 1) / big_band_rows();
     d->CW = (d->W + 1 <= 2048) ? 2048 : (d->W + 1 <= 4096 ? 4096 : 8192);
     const size_t B = (size_t)max_batch;
 #define ALLOC(ptr, bytes)                                    \
@@ -500,7 +579,7 @@ int surfhip_detector_create(surfhip_detector** out, const surfhip_param* param, 
         e = hipMalloc((void**)&(ptr), (bytes));              \
         if (e != hipSuccess) goto fail;                      \
     } while (0)
-    make_plan(d->P, d->oct, d->plan, max_batch);
+    make_plan(d->P, d->oct, d->sw, d->plan, max_batch);
     // the u8 kernels write the integral image: one stream; no kernel reads the u8 frames: integral first, one
     // stream; else: u8 kernels on the detector stream, the integral and the integral-image kernels beside them
     d->sched = d->plan.iiw ? kFused : !plan_reads_frames(d->plan) ? kIntegralFirst : kSideStream;
@@ -514,7 +593,7 @@ int surfhip_detector_create(surfhip_detector** out, const surfhip_param* param, 
     ALLOC(d->iib[0], B * d->P.ii_stride * sizeof(int32_t));
     d->ii = d->iib[0];
     ALLOC(d->resp, B * d->tot_osize * sizeof(float));
-    ALLOC(d->colsum, (size_t)integral_bands(d->H, B) * d->CW * sizeof(uint32_t));
+    ALLOC(d->colsum, (size_t)integral_bands(d->H, max_batch, d->sw) * d->CW * sizeof(uint32_t));
     ALLOC(d->cand, B * d->cap * sizeof(surfhip_point));
     ALLOC(d->keys, B * d->cap * sizeof(uint32_t));
     ALLOC(d->cand_count, B * sizeof(int));
@@ -634,7 +713,7 @@ int surfhip_run_integral(surfhip_detector* d, const uint8_t* frames, int nframes
     // a prefetch on the side stream may still be using the colsum scratch
     HIPCHK(side_before(d, d->stream));
     HIPCHK(source_frames(d, b, d->stream));
-    HIPCHK(launch_integral(b, d->P, d->colsum, d->ii, d->stream));
+    HIPCHK(launch_integral(b, d->P, d->sw, d->colsum, d->ii, d->stream));
     // (plan.iiw) the row sums a following run_hessian's k_hess_w adds: it
     // rewrites the same integral image
     HIPCHK(launch_rowseg(b, d->P, d->plan, d->rowseg, d->stream));
@@ -723,7 +802,7 @@ static int hessian_stage(surfhip_detector* d, const HessianArgs& a, bool have)
             // colsum scratch) is ordered first; it finished long ago.
             HIPCHK(mark(begin, s));
             if (!prof) HIPCHK(side_before(d, s));
-            if (!have) HIPCHK(launch_integral(a.b, d->P, d->colsum, d->ii, s));
+            if (!have) HIPCHK(launch_integral(a.b, d->P, d->sw, d->colsum, d->ii, s));
             HIPCHK(mark(mid, s));
             if (prof) HIPCHK(launch_hess_oct0(a, s));        // (the plan's own u8 launches are empty)
             if (prof) HIPCHK(launch_hess_w(a, s));
@@ -737,7 +816,7 @@ static int hessian_stage(surfhip_detector* d, const HessianArgs& a, bool have)
             HIPCHK(mark(begin, s));
             HIPCHK(hipEventRecord(d->fork, s));
             HIPCHK(hipStreamWaitEvent(d->side, d->fork, 0));
-            if (!have) HIPCHK(launch_integral(a.b, d->P, d->colsum, d->ii, d->side));
+            if (!have) HIPCHK(launch_integral(a.b, d->P, d->sw, d->colsum, d->ii, d->side));
             HIPCHK(launch_hess_ii(a, d->side));
             if (timed && side_hess) HIPCHK(hipEventRecord(hev[2], d->side));
             HIPCHK(launch_hess_oct0(a, s));
@@ -753,13 +832,12 @@ static int hessian_stage(surfhip_detector* d, const HessianArgs& a, bool have)
 // Where this call enqueues the next batch's prefetch.  Default: after this batch's Hessian, beside its NMS
 // scan, fit and sort (the Hessian and describe then run alone); a fused plan's prefetch is only the row-sum
 // pass and its default is before describe (its HBM use is low and describe's waves leave room for its
-// 16-VGPR waves).  SURFHIP_PREFETCH=describe / any other value (nms) overrides the default.  plan.rsum:
-// k_hess_p0 makes the row sums of its own batch, nothing to prefetch.
-static Prefetch prefetch_place(const LaunchPlan& plan, bool pipe)
+// 16-VGPR waves).  SURFHIP_PREFETCH=describe / any other value (nms), as the detector read it, overrides the
+// default.  plan.rsum: k_hess_p0 makes the row sums of its own batch, nothing to prefetch.
+static Prefetch prefetch_place(const LaunchPlan& plan, const Switches& sw, bool pipe)
 {
-    static const char* const env = getenv("SURFHIP_PREFETCH");
     if (!pipe || (plan.iiw && plan.rsum)) return kPrefNone;
-    return (env ? strcmp(env, "describe") != 0 : !plan.iiw) ? kPrefNms : kPrefDescribe;
+    return (sw.prefetch >= 0 ? sw.prefetch == 0 : !plan.iiw) ? kPrefNms : kPrefDescribe;
 }
 
 // The next batch's integral (into the other buffer; fused: its row sums) on the side stream, ordered after
@@ -772,7 +850,7 @@ static hipError_t prefetch_next(surfhip_detector* d, const FrameBatch& next, hip
     if (e == hipSuccess) e = hipStreamWaitEvent(d->side, d->fork2, 0);
     if (e == hipSuccess)
         e = d->sched == kFused ? launch_rowseg(next, d->P, d->plan, d->rowseg, d->side)
-                               : launch_integral(next, d->P, d->colsum, d->iib[nx], d->side);
+                               : launch_integral(next, d->P, d->sw, d->colsum, d->iib[nx], d->side);
     if (e != hipSuccess) return e;
     d->pref_valid = true;
     d->ipref = nx;
@@ -797,7 +875,7 @@ int surfhip_detect_batch_next(surfhip_detector* d, const uint8_t* frames, int nf
         rc = check_frames(d, next);
         if (rc) return rc;
     }
-    const Prefetch pf = prefetch_place(d->plan, pipe);
+    const Prefetch pf = prefetch_place(d->plan, d->sw, pipe);
     hipStream_t s = d->stream;
     // this batch's integral (fused: its row sums): prefetched by the previous
     // call (same frames), or computed now
@@ -816,20 +894,23 @@ int surfhip_detect_batch_next(surfhip_detector* d, const uint8_t* frames, int nf
     rc = hessian_stage(d, hessian_args(d, b), have);
     if (rc) return rc;
     if (pf == kPrefNms) HIPCHK(prefetch_next(d, next, s));
-    // getTrace in k_describe_u2 (its integral rows are in L2 there) rather
-    // than in the fit (16 scattered integral loads per survivor from HBM)
-    const bool trace_desc = desc && trace_in_describe(d->P, nframes);
+    // the describe kernel, and getTrace in k_describe_u2 (its integral rows
+    // are in L2 there) rather than in the fit (16 scattered integral loads per
+    // survivor from HBM); no describe: the fit takes it
+    DescribeChoice how = choose_describe(d->sw, d->P, nframes);
+    if (!desc) how.trace = false;
     HIPCHK(launch_nms(d->ii, d->resp, nframes, d->P, d->d_oct, d->plan, d->scan_key, d->scan_src, d->scan_cube,
-                      d->item_count, d->item_off, d->cand, d->keys, d->cand_count, d->cap, d->status, s, trace_desc));
+                      d->item_count, d->item_off, d->cand, d->keys, d->cand_count, d->cap, d->status, s, d->sw,
+                      how.trace));
     if (prof) HIPCHK(hipEventRecord(d->ev[3], s));
     HIPCHK(launch_sort(d->cand, d->keys, d->gscratch, d->cand_count, d->item_off, d->plan.nms_start[kMaxOct] * 4,
-                       d->cap, nframes, points, d->max_pts, counts, d->offsets, d->order, d->status, s));
+                       d->cap, nframes, points, d->max_pts, counts, d->offsets, d->order, d->status, s, d->sw));
     if (prof) HIPCHK(hipEventRecord(d->ev[4], s));
     if (pf == kPrefDescribe) HIPCHK(prefetch_next(d, next, s));
     if (d->desc_ev) HIPCHK(hipEventRecord(d->desc_ev, s));
     if (desc)
         HIPCHK(launch_describe(d->ii, d->P, points, d->max_pts, counts, d->offsets, d->order, d->work, nframes, desc,
-                               d->status + 64, s, pf == kPrefDescribe && !d->plan.iiw, d->cus, trace_desc));
+                               d->status + 64, s, pf == kPrefDescribe && !d->plan.iiw, d->cus, d->sw, how));
     if (prof) HIPCHK(hipEventRecord(d->ev[5], s));
     d->last = b;
     return SURFHIP_OK;
@@ -998,14 +1079,14 @@ long long surfhip_hessian_bytes_per_frame(surfhip_detector* d) { return d ? d->h
 
 int surfhip_hessian_plan(surfhip_detector* d, char* buf, int len)
 {
-    if (!d) return SURFHIP_ERR_INVALID;
-    const std::string t = hessian_plan_text(d->plan, d->P);
-    if (buf && len > 0) {
-        const size_t n = std::min((size_t)len - 1, t.size());
-        memcpy(buf, t.data(), n);
-        buf[n] = 0;
-    }
-    return (int)t.size();
+    return d ? text_out(hessian_plan_text(d->plan, d->P), buf, len) : SURFHIP_ERR_INVALID;
+}
+
+int surfhip_switches_from_env(char* buf, int len) { return text_out(switches_text(read_switches()), buf, len); }
+
+int surfhip_detector_switches(surfhip_detector* d, char* buf, int len)
+{
+    return d ? text_out(switches_text(d->sw), buf, len) : SURFHIP_ERR_INVALID;
 }
 
 size_t surfhip_slab_bytes(int nframes, int total, int nfeatures)

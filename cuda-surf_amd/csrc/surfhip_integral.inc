@@ -304,11 +304,12 @@ static void launch_bandscan(uint32_t* colsum, int nbands, int CW, int W, int nfr
     else k_ii_bandscan<272><<<dim3((W + 255) / 256, nframes), 256, 0, s>>>(colsum, nbands, CW, W);
 }
 
-hipError_t launch_integral(const FrameBatch& b, const FrameParams& P, uint32_t* colsum, int32_t* ii, hipStream_t s)
+hipError_t launch_integral(const FrameBatch& b, const FrameParams& P, const Switches& sw, uint32_t* colsum,
+                           int32_t* ii, hipStream_t s)
 {
     // small batches: 8-row bands (4x the band waves of the fill pass, which
     // is one wave per band) -- colsum is sized for both (integral_bands())
-    const int br = b.n <= kSmallBatch ? small_band_rows() : big_band_rows();
+    const int br = b.n <= kSmallBatch ? sw.ii_band_small : sw.ii_band;
     const int nbands = (P.H + br - 1) / br;
     const int W = P.W;
     dim3 grid(nbands, b.n);

@@ -27,31 +27,42 @@ constexpr int kDescQueueBytes = 8 * kDescQ * 64 * 4;
 constexpr int kBandRows = 32;       // integral-image band height
 constexpr int kBandRowsSmall = 16;  // ... for batches of <= kSmallBatch frames (one 1080p frame: 16 -> 0.1281-0.1287 ms vs 8 -> 0.1298-0.1305, 4 -> 0.131)
 constexpr int kSmallBatch = 8;
-// band height for batches > kSmallBatch: kBandRows, or SURFHIP_II_BAND (8..64)
-inline int big_band_rows()
-{
-    static const int v = [] {
-        const char* e = getenv("SURFHIP_II_BAND");
-        const int b = e ? atoi(e) : kBandRows;
-        return (b >= 8 && b <= 64) ? b : kBandRows;
-    }();
-    return v;
-}
-// band height for batches <= kSmallBatch: kBandRowsSmall, or
-// SURFHIP_II_BAND_SMALL (4..32; A/B)
-inline int small_band_rows()
-{
-    static const int v = [] {
-        const char* e = getenv("SURFHIP_II_BAND_SMALL");
-        const int b = e ? atoi(e) : kBandRowsSmall;
-        return (b >= 4 && b <= 32) ? b : kBandRowsSmall;
-    }();
-    return v;
-}
+// The run-time switches (the SURFHIP_* environment variables of INTEGRATION.md's
+// table).  A detector reads them once, when it is created (read_switches, the
+// library's only reader of the environment), and its plan, its scratch sizes
+// and every launch take them from there: a variable changed later does not
+// reach it.  Values are normalised by read_switches; -1: unset, where the
+// default depends on the detector or the batch.
+struct Switches {
+    unsigned set = 0;               // bit i: variable i, in the order below, was in the environment (switches_text)
+    // make_plan
+    int hess_gather = -1;           // HESS_GATHER 0 / 1; unset: max_batch <= kGatherBatch
+    bool hess_w = true;             // HESS_W
+    bool q01 = true;                // Q01
+    int p0 = 93;                    // P0: 0 (k_hess_q0), 95, 93, 92, 91, 32
+    bool hess_t0 = true;            // HESS_T0
+    int ii_fuse = 1;                // II_FUSE: 0, 1, 2
+    bool rowsum_rowseg = false;     // ROWSUM=rowseg
+    // choose_describe, launch_sort
+    int desc_ur = -1;               // DESC_UR 0 / 1; unset: batches <= kGatherBatch
+    bool trace_desc = true;         // TRACE_DESC
+    bool rot_atomic = false;        // ROT_ATOMIC: set to anything
+    bool sort_bitonic = false;      // SORT_BITONIC: set to anything
+    // prefetch_place, launch_describe, launch_nms, launch_integral
+    int prefetch = -1;              // PREFETCH 0 nms / 1 describe; unset: by the plan
+    int desc_beside = 3;            // DESC_BESIDE
+    int u2_ldspad = 0;              // U2_LDSPAD
+    int fit_grid = 1280;            // FIT_GRID: >= 64
+    bool fit_cube = true;           // FIT_CUBE
+    int ii_band = kBandRows;        // II_BAND 8..64: band height for batches > kSmallBatch
+    int ii_band_small = kBandRowsSmall;   // II_BAND_SMALL 4..32: ... for batches <= kSmallBatch
+};
+Switches read_switches();                       // from the environment (surfhip_api.hip)
+std::string switches_text(const Switches& sw);  // "NAME=value" of the variables that were set, or ""
 // colsum entries (per column) the integral of a batch of up to max_batch frames needs
-inline long long integral_bands(int H, int max_batch)
+inline long long integral_bands(int H, int max_batch, const Switches& sw)
 {
-    const int bb = big_band_rows(), sb = small_band_rows();
+    const int bb = sw.ii_band, sb = sw.ii_band_small;
     const long long big = (long long)max_batch * ((H + bb - 1) / bb);
     const long long small = (long long)(max_batch < kSmallBatch ? max_batch : kSmallBatch) * ((H + sb - 1) / sb);
     return big > small ? big : small;
@@ -112,7 +123,9 @@ inline bool operator==(const FrameBatch& a, const FrameBatch& b)
 {
     return a.frames == b.frames && a.n == b.n && a.pitch == b.pitch && a.stride == b.stride;
 }
-hipError_t launch_integral(const FrameBatch& b, const FrameParams& P, uint32_t* colsum, int32_t* ii, hipStream_t s);
+// (colsum: integral_bands() of the same switches)
+hipError_t launch_integral(const FrameBatch& b, const FrameParams& P, const Switches& sw, uint32_t* colsum,
+                           int32_t* ii, hipStream_t s);
 // Block ranges of the fused all-octave launches and the Hessian kernel of
 // each octave (computed once per detector; make_plan).
 struct LaunchPlan {
@@ -143,7 +156,7 @@ struct LaunchPlan {
 };
 // the plan has kernels that read the u8 frames (not only the integral image)
 inline bool plan_reads_frames(const LaunchPlan& p) { return p.q0 || p.q1 || p.hw_n > 0; }
-// max_batch <= kGatherBatch (or SURFHIP_HESS_GATHER=1; =0 disables) puts every
+// max_batch <= kGatherBatch (or Switches::hess_gather 1; 0 disables) puts every
 // octave on the one-thread-per-response gather kernel: the streaming kernels
 // walk whole strips, one wave each, too few waves to fill the chip for a few
 // frames (measured crossover, 1080p: gather 9,956 vs streaming 7,981 frames/s
@@ -151,7 +164,7 @@ inline bool plan_reads_frames(const LaunchPlan& p) { return p.q0 || p.q1 || p.hw
 constexpr int kGatherBatch = 8;
 // float4s per k_worklist entry (k_describe_u2's flattened schedule)
 constexpr int kWorkF4 = 3;
-void make_plan(const FrameParams& P, const OctaveParams* oct, LaunchPlan& plan, int max_batch);
+void make_plan(const FrameParams& P, const OctaveParams* oct, const Switches& sw, LaunchPlan& plan, int max_batch);
 // the Hessian stage's kernels of a plan, as text (surfhip_hessian_plan)
 std::string hessian_plan_text(const LaunchPlan& plan, const FrameParams& P);
 
@@ -185,31 +198,37 @@ hipError_t launch_rowseg(const FrameBatch& b, const FrameParams& P, const Launch
 hipError_t launch_nms(const int32_t* ii, const float* resp, int nframes, const FrameParams& P,
                       const OctaveParams* d_oct, const LaunchPlan& plan, uint32_t* scan_key, uint32_t* scan_src,
                       float* scan_cube, int* item_count, int* item_off, surfhip_point* cand, uint32_t* keys,
-                      int* cand_count, int cap, int* status, hipStream_t s, bool stash_trace);
+                      int* cand_count, int cap, int* status, hipStream_t s, const Switches& sw, bool stash_trace);
 hipError_t launch_sort(const surfhip_point* cand, const uint32_t* keys, uint64_t* gscratch,
                        const int* cand_count, const int* soff, int items_per_frame, int cap, int nframes,
                        surfhip_point* out, int max_pts, int* out_count, int* offsets, int* order, int* status,
-                       hipStream_t s);
+                       hipStream_t s, const Switches& sw);
 hipError_t set_max_lds(const void* fn, int bytes);
+// The describe kernel of a batch of nframes and where its laplace sign is
+// taken, chosen once per call (surfhip_detect_batch_next).  kDescU2: upright
+// 4 x 4 windows, the packed worklist fields large enough, and
+// SURFHIP_DESC_UR=0 or, unset, batches > kGatherBatch.  trace: the sign
+// (getTrace, surfd.cu:369-377) is taken in k_describe_u2, from the integral
+// rows the keypoint's window brings into L2, instead of in k_nms_fit: only on
+// kDescU2 with both integral extents below 32768; SURFHIP_TRACE_DESC=0 keeps
+// it in the fit (A/B).
+enum DescKernel { kDescU2, kDescUr, kDescWide, kDescUpright, kDescRot, kDescRotAtomic };
+struct DescribeChoice {
+    DescKernel kernel;
+    bool trace;
+};
+DescribeChoice choose_describe(const Switches& sw, const FrameParams& P, int nframes);
 // queue: kDescQueueBytes of device scratch (the per-XCD work counters of
 // k_describe_ur, 8 x kDescQ of them 256 B apart, zeroed by the launch)
 // beside: another stream's kernels (the next batch's integral, not a mere
 // row-sum pass) run beside it, so the persistent grid leaves each CU a workgroup slot
 // work: max_batch * max_pts * kWorkF4 float4 of scratch (k_describe_u2's flattened schedule)
 // cus: compute units of the detector's device (sizes the persistent grid)
-// trace: the fit left getTrace to the describe (trace_in_describe, the same
-// call's stash_trace of launch_nms)
+// how: the batch's choose_describe(); its trace was the same call's stash_trace of launch_nms
 hipError_t launch_describe(const int32_t* ii, const FrameParams& P, surfhip_point* pts, int max_pts,
                            const int* counts, const int* offsets, const int* order, float4* work, int nframes,
-                           float* desc, int* queue, hipStream_t s, bool beside, int cus, bool trace);
-// Whether a batch of nframes describes on k_describe_u2 (upright 4 x 4
-// windows, batches > kGatherBatch or SURFHIP_DESC_UR=0, packed worklist
-// fields large enough), and whether its laplace sign (getTrace,
-// surfd.cu:369-377) is then taken there, from the integral rows the
-// keypoint's window brings into L2, instead of in k_nms_fit
-// (SURFHIP_TRACE_DESC=0: in the fit, A/B)
-bool describe_on_u2(const FrameParams& P, int nframes);
-bool trace_in_describe(const FrameParams& P, int nframes);
+                           float* desc, int* queue, hipStream_t s, bool beside, int cus, const Switches& sw,
+                           DescribeChoice how);
 // Doubled-image input (surfhip_double.hip): frames (W x H) -> D ((2W-2) x
 // (2H-2) u8, row pitch dpitch, a multiple of 4).
 // HBM stream-rate kernels (surfhip_stream.hip): mode 0 copy, 1 read, 2 write

@@ -3,7 +3,7 @@
 // order is part of the build: k_hess_w's place in the code object matters).
 // This file keeps the shared device helpers, make_plan / hessian_plan_text,
 // the row-sum and generic Hessian kernels with the Hessian launchers,
-// k_worklist, launch_describe and k_pack.
+// k_worklist, choose_describe / launch_describe and k_pack.
 //
 // Stage map (reference file:line -> file -> kernels):
 //   integralRow/integralCol    surfd.cu:129-165, 2683-2704 -> surfhip_integral.inc -> k_ii_bandsum, k_ii_bandscan,
@@ -371,37 +371,31 @@ static int hw_octaves(const FrameParams& P, const OctaveParams* oct)
 //                 k_hess_q0 + k_hess_q1 in one launch (k_hess_q01) unless SURFHIP_Q01=0
 //   the rest      k_hessian, one thread per sample over the integral image
 //                 (every octave for batches <= kGatherBatch or SURFHIP_HESS_GATHER=1)
-void make_plan(const FrameParams& P, const OctaveParams* oct, LaunchPlan& plan, int max_batch)
+// (sw: the detector's switches, read when it was created)
+void make_plan(const FrameParams& P, const OctaveParams* oct, const Switches& sw, LaunchPlan& plan, int max_batch)
 {
     plan = LaunchPlan{};
     int hb = 0, nb = 0;
-    const char* ge = getenv("SURFHIP_HESS_GATHER");
-    const bool gather = ge ? atoi(ge) != 0 : max_batch <= kGatherBatch;
-    const char* we = getenv("SURFHIP_HESS_W");
-    plan.hw_n = (!gather && !(we && atoi(we) == 0)) ? hw_octaves(P, oct) : 0;
+    const bool gather = sw.hess_gather >= 0 ? sw.hess_gather != 0 : max_batch <= kGatherBatch;
+    plan.hw_n = (!gather && sw.hess_w) ? hw_octaves(P, oct) : 0;
     plan.hw_nstrips = (P.W + hw::ST - 1) / hw::ST;
     plan.hw_nblk = ((P.H / 4 + 1 + hw::U - 1) / hw::U) * hw::U;
     plan.q0 = !gather && P.noct > 0 && q0_ok(P, oct[0]);
     plan.q0_strips = (oct[0].sw + 63) / 64;
     plan.q1 = !gather && P.noct > 1 && plan.hw_n == 0 && q1_ok(P, oct[1]);
     plan.q1_strips = P.noct > 1 ? (oct[1].sw + 63) / 64 : 0;
-    const char* me = getenv("SURFHIP_Q01");
-    plan.q01 = plan.q0 && plan.q1 && !(me && atoi(me) == 0);
+    plan.q01 = plan.q0 && plan.q1 && sw.q01;
     // octave 0 on k_hess_p0 unless SURFHIP_P0=0; SURFHIP_P0=BG (value 10 B + G)
     // picks its barrier interval B (steps) and consumer waves G
-    const char* pe = getenv("SURFHIP_P0");
-    plan.p0 = (plan.q0 && !plan.q01) ? (pe ? atoi(pe) : 93) : 0;
-    if (plan.p0 != 0 && plan.p0 != 95 && plan.p0 != 93 && plan.p0 != 92 && plan.p0 != 91 && plan.p0 != 32)
-        plan.p0 = 93;
+    plan.p0 = (plan.q0 && !plan.q01) ? sw.p0 : 0;
     // the gather plan's octave 0 from LDS tiles (k_hessian_t0) when its
     // corners reach at most kT0Halo integral samples from the sample and the
     // sampling step is 2 (the default geometry); SURFHIP_HESS_T0=0 disables
     {
-        const char* te = getenv("SURFHIP_HESS_T0");
         const OctaveParams& q = oct[0];
         int reach = 0;
         for (int i = 0; i < q.nscale; i++) reach = std::max(reach, std::max(q.mask[i] + q.x2[i], q.x4[i]));
-        plan.t0 = gather && P.noct > 0 && q.delta == 2 && reach <= kT0Halo && !(te && atoi(te) == 0);
+        plan.t0 = gather && P.noct > 0 && q.delta == 2 && reach <= kT0Halo && sw.hess_t0;
         plan.t0_nbx = (q.sw + 63) / 64;
         plan.t0_nby = (q.sh + kT0BY - 1) / kT0BY;
     }
@@ -427,10 +421,8 @@ void make_plan(const FrameParams& P, const OctaveParams* oct, LaunchPlan& plan, 
     // k_hess_w; octaves past 3 (k_hessian) then read the integral written,
     // after them on the same stream
     {
-        const char* fe = getenv("SURFHIP_II_FUSE");
-        const int fv = fe ? atoi(fe) : 1;
-        const bool on = plan.hw_n >= 2 && plan.p0 != 0 && !plan.t0 && fv != 0;
-        plan.iiw = !on ? 0 : (fv == 2 && plan.p0 == 93) ? 2 : 1;
+        const bool on = plan.hw_n >= 2 && plan.p0 != 0 && !plan.t0 && sw.ii_fuse != 0;
+        plan.iiw = !on ? 0 : (sw.ii_fuse == 2 && plan.p0 == 93) ? 2 : 1;
         plan.rs_rows = 4 * plan.hw_nblk;
         plan.rs_nstrips = plan.iiw == 2 ? plan.q0_strips : plan.hw_nstrips;
         // k_hess_w's row sums from k_hess_p0's producers instead of
@@ -438,8 +430,7 @@ void make_plan(const FrameParams& P, const OctaveParams* oct, LaunchPlan& plan, 
         // octave 0 runs on the default k_hess_p0 (the RS instantiation) and
         // there is more than one k_hess_w strip; SURFHIP_ROWSUM=rowseg keeps
         // the pass (A/B), =p0 is the default
-        const char* re = getenv("SURFHIP_ROWSUM");
-        plan.rsum = plan.iiw == 1 && plan.p0 == 93 && plan.rs_nstrips >= 2 && !(re && !strcmp(re, "rowseg"));
+        plan.rsum = plan.iiw == 1 && plan.p0 == 93 && plan.rs_nstrips >= 2 && !sw.rowsum_rowseg;
     }
 }
 
@@ -697,7 +688,7 @@ __global__ __launch_bounds__(256) void k_worklist(const surfhip_point* __restric
     // left it to the describe, nms_fit_point):
     //   {dx, dy, spacing, f}  {ix, iy, step | hs << 10 | iradius << 22, f * max_pts + kp}
     //   {laplace, ori, 1 / spacing, 0}
-    // (10 / 12 / 10 bits: launch_describe takes this path only when the
+    // (10 / 12 / 10 bits: choose_describe takes this path only when the
     // largest window of the detector's octaves fits, worklist_fits)
     const int f = blockIdx.y, n = counts[f], o = offsets[f];
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
@@ -734,72 +725,73 @@ static bool worklist_fits(const FrameParams& P)
     return S * 0.5f + 1.f < 1024.f && S + 1.f < 4096.f && iradius < 1024.f;
 }
 
-bool describe_on_u2(const FrameParams& P, int nframes)
+DescribeChoice choose_describe(const Switches& sw, const FrameParams& P, int nframes)
 {
-    // SURFHIP_DESC_UR=1 / 0 forces k_describe_ur / k_describe_u2 (read per
-    // call, so a process can A/B both kernels); default: k_describe_ur for
-    // batches of <= kGatherBatch frames, where a wave gets about one keypoint
-    // and the ring's fill latency is not amortised -- one 1080p frame's
-    // describe 0.032 -> 0.030 ms
-    const char* ur = getenv("SURFHIP_DESC_UR");
-    const bool use_u2 = ur ? atoi(ur) == 0 : nframes > kGatherBatch;
-    return P.upright && P.wsz == 4 && use_u2 && worklist_fits(P);
-}
-
-bool trace_in_describe(const FrameParams& P, int nframes)
-{
-    const char* e = getenv("SURFHIP_TRACE_DESC");
-    // the fit's stash holds the box centre as two int16 (nms_fit_point,
-    // decoded signed in k_describe_u2): from integral row / column 32768 on
-    // the sign stays in the fit (trace_sign), whatever the switch says
-    const bool fits16 = P.iH < 32768 && P.W + 1 < 32768;
-    return (e ? atoi(e) != 0 : true) && fits16 && describe_on_u2(P, nframes);
+    // SURFHIP_DESC_UR=1 / 0 forces k_describe_ur / k_describe_u2; default:
+    // k_describe_ur for batches of <= kGatherBatch frames, where a wave gets
+    // about one keypoint and the ring's fill latency is not amortised -- one
+    // 1080p frame's describe 0.032 -> 0.030 ms
+    const bool want_u2 = sw.desc_ur >= 0 ? sw.desc_ur == 0 : nframes > kGatherBatch;
+    if (P.upright && P.wsz == 4) {
+        if (!(want_u2 && worklist_fits(P))) return {kDescUr, false};
+        // the fit's stash holds the box centre as two int16 (nms_fit_point,
+        // decoded signed in k_describe_u2): from integral row / column 32768 on
+        // the sign stays in the fit (trace_sign), whatever the switch says
+        const bool fits16 = P.iH < 32768 && P.W + 1 < 32768;
+        return {kDescU2, sw.trace_desc && fits16};
+    }
+    // windows past 4 x 4 x 8 (desc_wsz 5..7: up to 392 features)
+    if (P.nfeat > 128) return {kDescWide, false};
+    if (P.upright) return {kDescUpright, false};
+    return {P.wsz == 4 && !sw.rot_atomic ? kDescRot : kDescRotAtomic, false};
 }
 
 hipError_t launch_describe(const int32_t* ii, const FrameParams& P, surfhip_point* pts, int max_pts,
                            const int* counts, const int* offsets, const int* order, float4* work, int nframes,
-                           float* desc, int* queue, hipStream_t s, bool beside, int cus, bool trace)
+                           float* desc, int* queue, hipStream_t s, bool beside, int cus, const Switches& sw,
+                           DescribeChoice how)
 {
     if (P.nfeat > 512) return hipErrorInvalidValue;
     // the describe kernels are persistent (per-XCD keypoint queues): 2,048
     // workgroups fill every CU; with another stream's kernels beside them
     // (SURFHIP_DESC_BESIDE workgroups per CU, default 3) a slot stays free
     if (cus <= 0) cus = 256;
-    static const int per_cu = getenv("SURFHIP_DESC_BESIDE") ? atoi(getenv("SURFHIP_DESC_BESIDE")) : 3;
-    const int grid = (beside && per_cu > 0) ? ((per_cu * cus + 7) & ~7) : 2048;
+    const int grid = (beside && sw.desc_beside > 0) ? ((sw.desc_beside * cus + 7) & ~7) : 2048;
     hipError_t e = hipMemsetAsync(queue, 0, kDescQueueBytes, s);
     if (e != hipSuccess) return e;
-    // k_describe_u2 (LDS-DMA ring), else round 3's k_describe_ur
-    // (describe_on_u2); `trace` implies the u2 path (trace_in_describe)
-    const bool u2 = describe_on_u2(P, nframes);
-    if (trace && !u2) return hipErrorInvalidValue;
-    if (u2) {
-        k_worklist<<<dim3(std::min(8, (max_pts + 255) / 256), nframes), 256, 0, s>>>(pts, max_pts, counts, offsets,
-                                                                                      order, work, P);
-        // (diagnostic: SURFHIP_U2_LDSPAD bytes of unused dynamic LDS per workgroup)
-        static const int pad = getenv("SURFHIP_U2_LDSPAD") ? atoi(getenv("SURFHIP_U2_LDSPAD")) : 0;
-        const int tr = trace ? 1 : 0;
-        if (P.extend)
-            k_describe_u2<true><<<grid, 256, pad, s>>>(ii, P, work, max_pts, offsets, nframes, desc, queue, pts, tr);
-        else k_describe_u2<false><<<grid, 256, pad, s>>>(ii, P, work, max_pts, offsets, nframes, desc, queue, pts, tr);
-    } else if (P.upright && P.wsz == 4) {
-        if (P.extend)
-            k_describe_ur<true><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, offsets, order, nframes, desc, queue);
-        else k_describe_ur<false><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, offsets, order, nframes, desc, queue);
-    } else if (P.nfeat > 128) {
-        // windows past 4 x 4 x 8 (desc_wsz 5..7: up to 392 features)
-        if (P.upright)
-            k_describe<true, 512><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, counts, offsets, order, nframes, desc, queue);
-        else
-            k_describe<false, 512><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, counts, offsets, order, nframes, desc, queue);
-    } else if (P.upright) {
-        k_describe<true, 128><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, counts, offsets, order, nframes, desc, queue);
-    } else if (P.wsz == 4 && getenv("SURFHIP_ROT_ATOMIC") == nullptr) {
-        if (P.osz == 8)
-            k_describe_rot<8><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, offsets, order, nframes, desc, queue);
-        else k_describe_rot<4><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, offsets, order, nframes, desc, queue);
-    } else {
-        k_describe<false, 128><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, counts, offsets, order, nframes, desc, queue);
+    switch (how.kernel) {
+        case kDescU2: {         // the LDS-DMA ring
+            k_worklist<<<dim3(std::min(8, (max_pts + 255) / 256), nframes), 256, 0, s>>>(pts, max_pts, counts, offsets,
+                                                                                          order, work, P);
+            // (diagnostic: SURFHIP_U2_LDSPAD bytes of unused dynamic LDS per workgroup)
+            const int pad = sw.u2_ldspad, tr = how.trace ? 1 : 0;
+            if (P.extend)
+                k_describe_u2<true><<<grid, 256, pad, s>>>(ii, P, work, max_pts, offsets, nframes, desc, queue, pts, tr);
+            else k_describe_u2<false><<<grid, 256, pad, s>>>(ii, P, work, max_pts, offsets, nframes, desc, queue, pts, tr);
+            break;
+        }
+        case kDescUr:           // round 3's upright kernel
+            if (P.extend)
+                k_describe_ur<true><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, offsets, order, nframes, desc, queue);
+            else k_describe_ur<false><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, offsets, order, nframes, desc, queue);
+            break;
+        case kDescWide:
+            if (P.upright)
+                k_describe<true, 512><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, counts, offsets, order, nframes, desc, queue);
+            else
+                k_describe<false, 512><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, counts, offsets, order, nframes, desc, queue);
+            break;
+        case kDescUpright:
+            k_describe<true, 128><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, counts, offsets, order, nframes, desc, queue);
+            break;
+        case kDescRot:
+            if (P.osz == 8)
+                k_describe_rot<8><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, offsets, order, nframes, desc, queue);
+            else k_describe_rot<4><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, offsets, order, nframes, desc, queue);
+            break;
+        case kDescRotAtomic:
+            k_describe<false, 128><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, counts, offsets, order, nframes, desc, queue);
+            break;
     }
     return hipGetLastError();
 }

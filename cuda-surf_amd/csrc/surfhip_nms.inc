@@ -155,8 +155,8 @@ __device__ __forceinline__ int32_t trace_sign(const uint32_t* __restrict__ I, in
 // 942-1022) for one NMS survivor.
 // cube: the scan's record of the 19 responses around (s, r, c) (nullptr:
 // read them from the planes)
-// stash: leave getTrace to k_describe_u2 (trace_in_describe): laplace holds
-// its box centre x0 | y0 << 16 (int16 each: trace_in_describe keeps frames of
+// stash: leave getTrace to k_describe_u2 (choose_describe): laplace holds
+// its box centre x0 | y0 << 16 (int16 each: choose_describe keeps frames of
 // 32768 integral rows or more off this path) and ori the lobe `temp`, which
 // the describe kernel replaces by the sign and 0
 __device__ bool nms_fit_point(const uint32_t* __restrict__ I, const OctView& V, const FrameParams& P,
@@ -594,14 +594,6 @@ static void launch_excl_scan(const int* in, int n, int* out, int* bsum, hipStrea
     k_scan_add<<<nb, 256, 0, s>>>(out, n, bsum);
 }
 
-// k_nms_fit's grid: 5 waves per SIMD fit (90 VGPRs) = 1,280 workgroups of 4
-// waves; SURFHIP_FIT_GRID overrides (A/B)
-static int fit_grid()
-{
-    static const int g = getenv("SURFHIP_FIT_GRID") ? std::max(64, atoi(getenv("SURFHIP_FIT_GRID"))) : 1280;
-    return g;
-}
-
 // Pass 2: interpolation + makePoint, one lane per survivor of the whole batch
 // (grid-stride over the prefix of the scan items' survivor counts), so no
 // lane idles on the ~99 % of blocks that fail the 3x3x3 test and no
@@ -704,7 +696,7 @@ __global__ __launch_bounds__(256) void k_nms_fit(const int32_t* __restrict__ ii,
 hipError_t launch_nms(const int32_t* ii, const float* resp, int nframes, const FrameParams& P,
                       const OctaveParams* d_oct, const LaunchPlan& plan, uint32_t* scan_key, uint32_t* scan_src,
                       float* scan_cube, int* item_count, int* item_off, surfhip_point* cand, uint32_t* keys,
-                      int* cand_count, int cap, int* status, hipStream_t s, bool stash_trace)
+                      int* cand_count, int cap, int* status, hipStream_t s, const Switches& sw, bool stash_trace)
 {
     const int per = plan.nms_start[kMaxOct];
     if (per == 0) {
@@ -715,16 +707,16 @@ hipError_t launch_nms(const int32_t* ii, const float* resp, int nframes, const F
     }
     // the scan's fit records for every batch size (round 5: one 1080p frame's
     // NMS 0.038 -> 0.034 ms with them; round 2's cross-lane variant had made
-    // single frames slower)
-    static const char* ce = getenv("SURFHIP_FIT_CUBE");                  // A/B: 0 off, 1 on
-    const bool cube = ce ? atoi(ce) != 0 : true;
+    // single frames slower); SURFHIP_FIT_CUBE=0: the fit reads the planes (A/B)
+    const bool cube = sw.fit_cube;
     if (!cube) scan_cube = nullptr;
     auto* scan = cube ? &k_nms_scan<true> : &k_nms_scan<false>;
     scan<<<dim3(frame_grid(nframes) * per), 256, 0, s>>>(resp, P, d_oct, plan, scan_key, scan_src, scan_cube,
                                                                 item_count, nframes, cand_count, status);
     const int nitems = nframes * per * 4;
     launch_excl_scan(item_count, nitems, item_off, item_off + nitems + 1, s);
-    k_nms_fit<<<fit_grid(), 256, 0, s>>>(ii, resp, P, d_oct, scan_key, scan_src, scan_cube, item_off, nitems, per * 4,
-                                         cand, keys, cand_count, cap, stash_trace ? 1 : 0);
+    // 5 waves per SIMD fit (90 VGPRs) = 1,280 workgroups of 4 waves; SURFHIP_FIT_GRID overrides (A/B)
+    k_nms_fit<<<sw.fit_grid, 256, 0, s>>>(ii, resp, P, d_oct, scan_key, scan_src, scan_cube, item_off, nitems, per * 4,
+                                          cand, keys, cand_count, cap, stash_trace ? 1 : 0);
     return hipGetLastError();
 }

@@ -337,9 +337,9 @@ __global__ __launch_bounds__(1024) void k_offsets(const int* __restrict__ counts
 hipError_t launch_sort(const surfhip_point* cand, const uint32_t* keys, uint64_t* gscratch,
                        const int* cand_count, const int* soff, int items_per_frame, int cap, int nframes,
                        surfhip_point* out, int max_pts, int* out_count, int* offsets, int* order, int* status,
-                       hipStream_t s)
+                       hipStream_t s, const Switches& sw)
 {
-    if (nframes <= kRankBatch && getenv("SURFHIP_SORT_BITONIC") == nullptr) {
+    if (nframes <= kRankBatch && !sw.sort_bitonic) {
         // workgroups per frame: one per 16 candidates up to 256 (~3,000
         // candidates of a 1080p frame: 188), beyond that each takes several
         // groups of 16 with the keys it staged once

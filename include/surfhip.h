@@ -257,6 +257,17 @@ long long surfhip_hessian_bytes_per_frame(surfhip_detector* det);
  * 2-3)"), NUL-terminated in buf[len]; returns the full length. */
 int surfhip_hessian_plan(surfhip_detector* det, char* buf, int len);
 
+/* The run-time switches (the SURFHIP_* environment variables of
+ * INTEGRATION.md) as text: "NAME=value" of each variable that is set, its
+ * value normalised as the library takes it, separated by single spaces; ""
+ * when none is.  A detector reads them once, when it is created:
+ * surfhip_detector_switches gives what that detector holds,
+ * surfhip_switches_from_env what one created now would (no GPU needed).
+ * Like surfhip_hessian_plan, both return the full length and NUL-terminate
+ * what fits in buf[len]. */
+int surfhip_switches_from_env(char* buf, int len);
+int surfhip_detector_switches(surfhip_detector* det, char* buf, int len);
+
 /* Result slab for the multi-GPU all-gather, compacted to the
  * keypoints actually found by the last detect_batch:
  *   int32 {nframes, total, nfeatures (0 without descriptors), flags}

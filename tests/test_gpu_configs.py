@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 from conftest import assert_points_equal, desc_l2
-from test_gpu_parity import DESC_TOL, compare_frame, gpu_run
+from test_gpu_parity import DESC_TOL, compare_frame, gpu_run, took
 
 pytestmark = pytest.mark.gpu
 
@@ -81,6 +81,7 @@ def test_config3_describe_u2_deterministic(surf, monkeypatch, config3):
     again = gpu_run(surf, param, frames, W3, H3, max_pts=8192)
     monkeypatch.setenv("SURFHIP_DESC_UR", "1")
     ur = gpu_run(surf, param, frames, W3, H3, max_pts=8192)
+    assert took(ur, "SURFHIP_DESC_UR=1"), ur["switches"]
     for f in range(frames.shape[0]):
         assert again["counts"][f] == res["counts"][f] == ur["counts"][f], f
         assert again["desc"][f].tobytes() == res["desc"][f].tobytes(), f
@@ -197,6 +198,7 @@ def test_gather_plan_cases(surf, orc, monkeypatch, case):
     frames = surf.synth_frames(2, w, h, first=77)
     param = surf.make_param(noct, 4.0, doubled=doubled, upright=upright, extend=extend)
     res = gpu_run(surf, param, frames, w, h)
+    assert took(res, "SURFHIP_HESS_GATHER=1"), res["switches"]
     op = orc.make_param(noct, 4.0, doubled=doubled, upright=upright, extend=extend)
     for f in range(2):
         o_pts, o_desc, _ = orc.detect(op, frames[f], w, h)

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import assert_points_equal
-from test_gpu_parity import _plane_views, compare_frame, gpu_run      # compare_frame: descriptors within DESC_TOL
+from test_gpu_parity import _plane_views, compare_frame, gpu_run, took    # compare_frame: descriptors within DESC_TOL
 
 pytestmark = pytest.mark.gpu
 
@@ -63,7 +63,7 @@ def run_layout(surf, param, imgs, pitch, stride, lead, fill, max_pts=16384, desc
            "cand": det.candidates(n), "truncated": det.truncated(), "capacity": det.capacity(),
            "ii": surf.download_ptr(ii, np.int32, n * iis).reshape(n, -1),
            "resp": surf.download_ptr(rs, np.float32, n * rss).reshape(n, -1),
-           "geom": det.geometry(), "plan": det.hessian_kernels(), "frames": views}
+           "geom": det.geometry(), "plan": det.hessian_kernels(), "switches": det.switches(), "frames": views}
     det.close()
     return out
 
@@ -186,6 +186,7 @@ def test_layout_matrix(surf, orc, monkeypatch, plan, si, gap, lead, fill):
     imgs = pixels(surf, n, w, h)
     gp, op = params(surf, orc, upright=True, doubled=doubled)
     res = run_layout(surf, gp, imgs, pitch, h * pitch + gap, lead, fill)
+    assert took(res, "" if doubled else plan), res["switches"]
     for text in PLAN_TEXT[plan]:
         assert text in res["plan"], res["plan"]
     if plan == "SURFHIP_II_FUSE=0":
@@ -214,6 +215,7 @@ def test_layout_batch17(surf, orc, monkeypatch, plan):
     imgs = pixels(surf, n, w, h)
     gp, op = params(surf, orc, upright=True)
     res = run_layout(surf, gp, imgs, pitch, h * pitch + 48, 16, "rand", max_pts=2048)
+    assert took(res, plan), res["switches"]
     for text in PLAN_TEXT[plan]:
         assert text in res["plan"], res["plan"]
     for f in (0, 15, 16):
@@ -280,7 +282,7 @@ def test_detect_batch_next_other_layout(surf, monkeypatch, plan):
 # --------------------------------------------------------- B. sampling steps
 def run_sampling(surf, orc, monkeypatch, w, h, n, check, min_pts, noct=4, **kw):
     """Frames in the usual layout through a detector of the given parameters,
-    frames `check` against the oracle."""
+    frames `check` against the oracle; returns gpu_run's result."""
     set_plan(monkeypatch, "")
     imgs = pixels(surf, n, w, h)
     frames = padded(surf, imgs)
@@ -289,6 +291,7 @@ def run_sampling(surf, orc, monkeypatch, w, h, n, check, min_pts, noct=4, **kw):
     for f in check:
         ref = oracle_frame(orc, op, ("B", w, h, noct, tuple(sorted(kw.items())), f), frames[f], w, h)
         check_frame(res, f, ref, op, min_pts)
+    return res
 
 
 # sampling step, W, H, octaves, least oracle keypoints of the frames checked
@@ -319,7 +322,8 @@ def test_sampling_steps_batch12(surf, orc, monkeypatch, step, w, h, min_pts):
     getTrace from the fit's stash) at sampling steps 1 and 3."""
     monkeypatch.delenv("SURFHIP_TRACE_DESC", raising=False)
     monkeypatch.setenv("SURFHIP_DESC_UR", "0")
-    run_sampling(surf, orc, monkeypatch, w, h, 12, (0, 5, 11), min_pts, sampling_step=step, upright=True)
+    res = run_sampling(surf, orc, monkeypatch, w, h, 12, (0, 5, 11), min_pts, sampling_step=step, upright=True)
+    assert took(res, "SURFHIP_DESC_UR=0") and "SURFHIP_TRACE_DESC" not in res["switches"], res["switches"]
 
 
 def test_sampling_step3_doubled(surf, orc, monkeypatch):
@@ -354,6 +358,7 @@ def test_doubled_step1_streaming_plan(surf, orc, monkeypatch, plan):
     gp, op = params(surf, orc, sampling_step=1, doubled=True, upright=True)
     assert gp.sampling == 2
     res = run_layout(surf, gp, imgs, pitch, h * pitch + 48, 16, "rand")
+    assert took(res, plan), res["switches"]
     if plan in ("", "SURFHIP_II_FUSE=2"):
         assert "k_hess_p0" in res["plan"] and "writing the integral image" in res["plan"], res["plan"]
         assert ("(k_hess_p0)" in res["plan"]) == (plan != "")
@@ -388,6 +393,7 @@ def test_tall_frame_rows_past_32767(surf, orc, monkeypatch, trace_desc):
     assert len(o_pts) >= 11000 and len(low) >= 200
     assert (low["laplace"] == 1).any() and (low["laplace"] == -1).any()
     res = gpu_run(surf, gp, frames, w, h, max_pts=16384)
+    assert took(res, "SURFHIP_DESC_UR=0" + (f",SURFHIP_TRACE_DESC={trace_desc}" if trace_desc else "")), res["switches"]
     assert not res["truncated"] and res["cand"][0] == nc
     got = res["pts"][0]
     assert len(got) == len(o_pts)

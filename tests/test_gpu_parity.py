@@ -37,7 +37,8 @@ def gpu_run(surf, param, frames, w, h, max_pts=16384, desc=True, want_ws=False, 
     ds = db.download(np.float32, n * max_pts * nf).reshape(n, max_pts, nf) if desc else None
     out = {"counts": counts, "pts": [pts[f, :counts[f]] for f in range(n)],
            "desc": [ds[f, :counts[f]] for f in range(n)] if desc else None,
-           "cand": det.candidates(n), "truncated": det.truncated(), "capacity": det.capacity()}
+           "cand": det.candidates(n), "truncated": det.truncated(), "capacity": det.capacity(),
+           "switches": det.switches()}
     if want_ws:
         ii, iis, rs, rss = det.workspace()
         out["ii"] = surf.download_ptr(ii, np.int32, n * iis).reshape(n, -1)
@@ -45,6 +46,13 @@ def gpu_run(surf, param, frames, w, h, max_pts=16384, desc=True, want_ws=False, 
         out["geom"] = det.geometry()
     det.close()
     return out
+
+
+def took(res, env):
+    """Whether the detector behind `res` (gpu_run, run_layout) held every
+    NAME=value of `env` (comma-separated, "" = none) among its switches: a
+    test of a switched path cannot pass without the path it names."""
+    return set(filter(None, env.split(","))) <= set(res["switches"].split())
 
 
 def compare_frame(g_pts, g_desc, o_pts, o_desc, upright):
@@ -158,6 +166,7 @@ def test_hessian_planes_extreme_frames(surf, orc, monkeypatch, kind, env):
     frames = _extreme_frame(kind, w, h, surf.align_up(w, 128))[None]
     param = surf.make_param(4, 4.0, upright=True)
     res = gpu_run(surf, param, frames, w, h, want_ws=True, desc=False)
+    assert took(res, env), res["switches"]
     op = orc.make_param(4, 4.0, upright=True)
     _, ref, g, octs = orc.hessian(op, frames[0], w, h)
     got = res["resp"][0]
@@ -183,6 +192,7 @@ def test_hessian_alternate_kernels_bit_exact(surf, orc, monkeypatch, env, w, h, 
     frames = surf.synth_frames(1, w, h, first=21)
     param = surf.make_param(noct, 4.0, upright=True)
     res = gpu_run(surf, param, frames, w, h, want_ws=True, desc=False)
+    assert took(res, env), res["switches"]
     op = orc.make_param(noct, 4.0, upright=True)
     _, ref, g, octs = orc.hessian(op, frames[0], w, h)
     got = res["resp"][0]
@@ -207,13 +217,16 @@ def test_detect_describe_synthetic(surf, orc, upright, extend):
 @pytest.mark.parametrize("cube", ["0", "1"])
 def test_fit_records_from_scan(surf, orc, monkeypatch, cube):
     """k_nms_fit's first pass from the scan's record of the 19 responses
-    (SURFHIP_FIT_CUBE=1, the default for batches > 8) or from the planes
-    (=0, the small-batch default): the same keypoints, bit for bit."""
+    (SURFHIP_FIT_CUBE=1, k_nms_scan<true>, the default for every batch size)
+    or from the planes (=0, k_nms_scan<false>): the same keypoints, bit for
+    bit.  The detector reads the switch when it is created; its switches
+    text shows it took this one."""
     monkeypatch.setenv("SURFHIP_FIT_CUBE", cube)
     w, h = 640, 480
     frames = surf.synth_frames(3, w, h, first=300)
     param = surf.make_param(4, 4.0, upright=True)
     res = gpu_run(surf, param, frames, w, h)
+    assert took(res, f"SURFHIP_FIT_CUBE={cube}"), res["switches"]
     op = orc.make_param(4, 4.0, upright=True)
     for f in range(3):
         o_pts, o_desc, nc = orc.detect(op, frames[f], w, h)
@@ -233,6 +246,7 @@ def test_laplace_in_fit_or_describe(surf, orc, monkeypatch, trace_desc, desc):
     frames = surf.synth_frames(12, w, h, first=700)
     param = surf.make_param(4, 4.0, upright=True)
     res = gpu_run(surf, param, frames, w, h, desc=desc)
+    assert took(res, f"SURFHIP_TRACE_DESC={trace_desc}"), res["switches"]
     op = orc.make_param(4, 4.0, upright=True)
     for f in (0, 5, 11):
         o_pts, o_desc, nc = orc.detect(op, frames[f], w, h)
@@ -256,6 +270,7 @@ def test_rotated_descriptor_kernels(surf, orc, monkeypatch, extend, atomic):
     frames = surf.synth_frames(2, w, h, first=300)
     param = surf.make_param(5, 4.0, upright=False, extend=extend)
     res = gpu_run(surf, param, frames, w, h)
+    assert took(res, "SURFHIP_ROT_ATOMIC=1" if atomic else ""), res["switches"]
     op = orc.make_param(5, 4.0, upright=False, extend=extend)
     for f in range(2):
         o_pts, o_desc, _ = orc.detect(op, frames[f], w, h)

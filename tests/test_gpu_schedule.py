@@ -250,7 +250,7 @@ print("piped", piped.hexdigest())
 
 @pytest.mark.parametrize("plan", ["SURFHIP_ROWSUM=rowseg", "SURFHIP_II_FUSE=0"])
 def test_prefetch_env_values(plan):
-    """SURFHIP_PREFETCH (read once per process) unset, nms, describe and an
+    """SURFHIP_PREFETCH (one child process per value) unset, nms, describe and an
     unlisted value, where the prefetch is the row-sum pass and where it is the
     integral: the pipelined sequence A -> B, B -> A, A -> none hashes like the
     same batches through detect_batch, in every child alike."""

@@ -3,8 +3,8 @@
 cnt near the candidate capacity).  A uniform-noise frame gives ~10^4
 candidates; the stage is timed with the detector's profiling events, rank
 sort (default for <= 8 frames) against the bitonic k_sort
-(SURFHIP_SORT_BITONIC, read per launch), and the keypoints of both must be
-identical.
+(SURFHIP_SORT_BITONIC, read when a detector is created: one detector per
+mode), and the keypoints of both must be identical.
 
     python3 tools/sort_dense.py [thresh ...]
 """
@@ -30,7 +30,6 @@ def main():
     out = []
     for thresh in [float(a) for a in sys.argv[1:]] or [4.0, 40.0]:
         param = surf.make_param(4, thresh, upright=True)
-        det = surf.Detector(param, w, h, max_batch=1, max_pts=16384)
         pb = surf.DeviceBuffer(48 * 16384)
         db = surf.DeviceBuffer(4 * 64 * 16384)
         cb = surf.DeviceBuffer(4)
@@ -41,6 +40,8 @@ def main():
                 os.environ["SURFHIP_SORT_BITONIC"] = "1"
             else:
                 os.environ.pop("SURFHIP_SORT_BITONIC", None)
+            det = surf.Detector(param, w, h, max_batch=1, max_pts=16384)
+            assert ("SURFHIP_SORT_BITONIC=1" in det.switches()) == (mode == "bitonic"), det.switches()
             det.set_profiling(True)
             acc = []
             for i in range(25):
@@ -54,10 +55,10 @@ def main():
             pts[mode] = pb.download(surf.POINT_DTYPE, n)
             res[f"{mode}_sort_ms"] = round(float(np.median(acc)), 4)
             res["keypoints"] = n
-        res["candidates"] = int(det.candidates(1)[0])
+            res["candidates"] = int(det.candidates(1)[0])
+            det.close()
         res["identical"] = bool(pts["rank"].tobytes() == pts["bitonic"].tobytes())
         os.environ.pop("SURFHIP_SORT_BITONIC", None)
-        det.close()
         print(json.dumps(res), flush=True)
         out.append(res)
     if not all(r["identical"] for r in out):
