@@ -119,6 +119,7 @@ _sigs = {
     "surfhip_detector_rowsums": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "surfhip_run_integral": (_i, [_vp, _vp, _i, _i, _sz]),
     "surfhip_run_hessian": (_i, [_vp, _i]),
+    "surfhip_run_describe": (_i, [_vp, _vp, _vp, _i, _vp]),
     "surfhip_hessian_bytes_per_frame": (C.c_longlong, [_vp]),
     "surfhip_hessian_plan": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "surfhip_switches_from_env": (C.c_int, [C.c_char_p, C.c_int]),
@@ -384,6 +385,11 @@ class Detector:
 
     def run_hessian(self, nframes) -> None:
         check(_lib.surfhip_run_hessian(self.h, nframes), "run_hessian")
+
+    def run_describe(self, points_ptr, counts_ptr, nframes, desc_ptr) -> None:
+        """The describe stage on caller-given points [nframes][max_pts] and device counts, on the
+        integral images of the last run_integral / detect_batch (surfhip_run_describe)."""
+        check(_lib.surfhip_run_describe(self.h, points_ptr, counts_ptr, nframes, desc_ptr), "run_describe")
 
     def candidates(self, nframes: int) -> np.ndarray:
         out = np.zeros(nframes, np.int32)

@@ -96,6 +96,7 @@ struct surfhip_detector {
     int nitems = 0;                     // scan items per frame
     int* offsets = nullptr;
     int* order = nullptr;               // per frame: keypoint indices in row order (describe schedule)
+    int* pcount = nullptr;              // surfhip_run_describe: the caller's counts cut to [0, max_pts]
     float4* work = nullptr;             // the describe schedule flattened: kWorkF4 float4 per keypoint (k_worklist)
     int* status = nullptr;
     // single-frame API slots
@@ -511,7 +512,7 @@ static void free_all(surfhip_detector* d)
 {
     void* ptrs[] = {d->d_oct, d->iib[0], d->iib[1], d->resp, d->colsum, d->rowseg, d->psum, d->cand, d->keys, d->gscratch, d->cand_count,
                     d->scan_key, d->scan_src, d->scan_cube, d->item_count, d->item_off,
-                    d->offsets, d->order, d->work, d->status, d->pts1, d->desc1, d->count1, d->dbl};
+                    d->offsets, d->order, d->pcount, d->work, d->status, d->pts1, d->desc1, d->count1, d->dbl};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (int i = 0; i < SURFHIP_NSTAGE; i++)
@@ -606,6 +607,7 @@ int surfhip_detector_create(surfhip_detector** out, const surfhip_param* param, 
     ALLOC(d->item_off, (2 * B * (size_t)d->nitems + 64) * sizeof(int));
     ALLOC(d->offsets, (B + 1) * sizeof(int));
     ALLOC(d->order, B * (size_t)max_pts * sizeof(int));
+    ALLOC(d->pcount, B * sizeof(int));
     ALLOC(d->work, B * (size_t)max_pts * kWorkF4 * sizeof(float4));
     ALLOC(d->status, 256 + kDescQueueBytes);    // [0]: flags; from [64]: describe work queues
     ALLOC(d->pts1, (size_t)max_pts * sizeof(surfhip_point));
@@ -733,6 +735,21 @@ int surfhip_run_hessian(surfhip_detector* d, int nframes)
     HIPCHK(launch_hess_oct0(a, d->stream));
     HIPCHK(launch_hess_w(a, d->stream));
     HIPCHK(launch_hess_ii(a, d->stream));
+    return SURFHIP_OK;
+}
+
+// The describe stage of detect_batch on caller-given points: launch_plant's schedule (the identity order) in
+// place of launch_sort's, then the same choose_describe and launch_describe on the resident integral.  The
+// laplace sign stays where the caller put it (the fit's stash is what k_describe_u2 would take it from).
+int surfhip_run_describe(surfhip_detector* d, surfhip_point* points, const int* counts, int nframes, float* desc)
+{
+    if (!d || !points || !counts || !desc || nframes < 1 || nframes > d->max_batch) return SURFHIP_ERR_INVALID;
+    if (!d->last.frames) return SURFHIP_ERR_INVALID;    // no run_integral / detect_batch yet: no integral
+    DescribeChoice how = choose_describe(d->sw, d->P, nframes);
+    how.trace = false;
+    HIPCHK(launch_plant(counts, nframes, d->max_pts, d->pcount, d->offsets, d->order, d->stream));
+    HIPCHK(launch_describe(d->ii, d->P, points, d->max_pts, d->pcount, d->offsets, d->order, d->work, nframes, desc,
+                           d->status + 64, d->stream, false, d->cus, d->sw, how));
     return SURFHIP_OK;
 }
 

@@ -229,6 +229,12 @@ hipError_t launch_describe(const int32_t* ii, const FrameParams& P, surfhip_poin
                            const int* counts, const int* offsets, const int* order, float4* work, int nframes,
                            float* desc, int* queue, hipStream_t s, bool beside, int cus, const Switches& sw,
                            DescribeChoice how);
+// The describe schedule of caller-given points (surfhip_run_describe), in
+// place of launch_sort's: clamped[f] = counts[f] cut to [0, max_pts] (the
+// caller's counts stay as they are), their prefix in offsets (k_offsets) and
+// the identity order of each frame's first clamped[f] slots.
+hipError_t launch_plant(const int* counts, int nframes, int max_pts, int* clamped, int* offsets, int* order,
+                        hipStream_t s);
 // Doubled-image input (surfhip_double.hip): frames (W x H) -> D ((2W-2) x
 // (2H-2) u8, row pitch dpitch, a multiple of 4).
 // HBM stream-rate kernels (surfhip_stream.hip): mode 0 copy, 1 read, 2 write

@@ -851,4 +851,25 @@ hipError_t launch_pack(const surfhip_point* pts, const float* desc, const int* c
     return hipGetLastError();
 }
 
+// surfhip_run_describe's schedule (launch_plant).  A template, instantiated
+// here at the end of the file, so that it is the code object's last kernel:
+// the other kernels keep their places relative to each other.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void k_plant(const int* __restrict__ counts, int max_pts,
+                                                   int* __restrict__ clamped, int* __restrict__ order)
+{
+    const int f = blockIdx.y, n = min(max(counts[f], 0), max_pts);
+    if (blockIdx.x == 0 && threadIdx.x == 0) clamped[f] = n;
+    for (int i = blockIdx.x * THREADS + threadIdx.x; i < n; i += gridDim.x * THREADS)
+        order[(size_t)f * max_pts + i] = i;
+}
+
+hipError_t launch_plant(const int* counts, int nframes, int max_pts, int* clamped, int* offsets, int* order,
+                        hipStream_t s)
+{
+    k_plant<256><<<dim3(std::min(8, (max_pts + 255) / 256), nframes), 256, 0, s>>>(counts, max_pts, clamped, order);
+    k_offsets<<<1, 1024, 0, s>>>(clamped, nframes, offsets);
+    return hipGetLastError();
+}
+
 }  // namespace surfhip

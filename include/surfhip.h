@@ -248,6 +248,20 @@ int surfhip_run_integral(surfhip_detector* det, const uint8_t* d_frames, int nfr
                          int pitch, size_t frame_stride);
 int surfhip_run_hessian(surfhip_detector* det, int nframes);
 
+/* The describe stage alone, on caller-given points and the integral images
+ * the last run_integral or detect_batch left resident (SURFHIP_ERR_INVALID if
+ * there was none): d_points[nframes][max_pts], frame f's first
+ * clamp(d_counts[f], 0, max_pts) slots in slot order, described into
+ * d_desc[nframes][max_pts][nfeatures] with the kernel, grid and schedule a
+ * detect_batch of nframes frames would use (the order array is the
+ * identity).  A rotated detector also writes `ori` of exactly those points;
+ * no other point field, no slot at or past the count and no count is written
+ * (the laplace sign stays the caller's).  Asynchronous on the detector's
+ * stream.  The detector's batch schedule (surfhip_batch_total, the offsets
+ * surfhip_pack_slab uses) is then that of these counts. */
+int surfhip_run_describe(surfhip_detector* det, surfhip_point* d_points, const int* d_counts, int nframes,
+                         float* d_desc);
+
 /* Algorithmic (compulsory) HBM bytes per frame of the Hessian stage:
  * integral image read once + valid responses written. */
 long long surfhip_hessian_bytes_per_frame(surfhip_detector* det);

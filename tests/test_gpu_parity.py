@@ -359,6 +359,73 @@ def test_max_pts_cap_keeps_canonical_prefix(surf, orc):
     assert_points_equal(part["pts"][0], o_pts)
 
 
+@pytest.mark.parametrize("name,par,env,exact", [
+    ("u2", dict(upright=True), "SURFHIP_DESC_UR=0", True),                    # k_describe_u2
+    ("ur", dict(upright=True), "SURFHIP_DESC_UR=1", True),                    # k_describe_ur
+    ("rot", dict(upright=False), "", True),                                   # k_describe_rot
+    ("generic", dict(upright=True, desc_wsz=3), "", False)])                  # k_describe (LDS float atomics)
+def test_max_pts_cap_multi_frame_batch(surf, monkeypatch, name, par, env, exact):
+    """A 3-frame batch whose max_pts is below every frame's count: each frame keeps the first max_pts
+    keypoints of the uncapped run with their descriptors (byte-equal on the kernels without float
+    atomics, within DESC_TOL on the generic one), and nothing is written behind the point, descriptor
+    and count arrays."""
+    for kv in filter(None, env.split(",")):
+        k, _, v = kv.partition("=")
+        monkeypatch.setenv(k, v)
+    w, h, n = 640, 480, 3
+    frames = surf.synth_frames(n, w, h, first=3)
+    param = surf.make_param(4, 4.0, **par)
+    nf = param.nfeatures
+    full = gpu_run(surf, param, frames, w, h, max_pts=16384)
+    assert took(full, env), full["switches"]
+    cap = int(full["counts"].min()) // 2
+    assert cap >= 64
+    tail, canary = 4096, 0x5C
+    det = surf.Detector(param, w, h, max_batch=n, max_pts=cap)
+    fb = surf.DeviceBuffer(frames.nbytes)
+    fb.upload(frames)
+    sizes = (48 * n * cap, 4 * n * cap * nf, 4 * n)
+    bufs = [surf.DeviceBuffer(s + tail) for s in sizes]
+    for b in bufs:
+        b.upload(np.full(b.nbytes, canary, np.uint8))
+    pitch = frames.shape[2]
+    det.detect_batch(fb.ptr, n, pitch, h * pitch, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr)
+    surf.synchronize()
+    assert took({"switches": det.switches()}, env), det.switches()
+    raw = [b.download(np.uint8, b.nbytes) for b in bufs]
+    det.close()
+    for r, s in zip(raw, sizes):
+        assert (r[s:] == canary).all(), "canary behind an output array changed"
+    counts = raw[2][:sizes[2]].view(np.int32)
+    pts = raw[0][:sizes[0]].view(surf.POINT_DTYPE).reshape(n, cap)
+    desc = raw[1][:sizes[1]].view(np.float32).reshape(n, cap, nf)
+    assert (counts == cap).all(), counts
+    for f in range(n):
+        assert_points_equal(pts[f], full["pts"][f][:cap],
+                            fields=("x", "y", "scale", "o", "strength", "laplace", "ori"))
+        if exact:
+            assert desc[f].tobytes() == full["desc"][f][:cap].tobytes(), f"frame {f}"
+        else:
+            assert desc_l2(desc[f], full["desc"][f][:cap]).max() <= DESC_TOL
+
+
+@pytest.mark.parametrize("upright", [True, False])
+@pytest.mark.parametrize("w,h", [(64, 48), (100, 96), (128, 72)])
+def test_tiny_noise_frames_match_oracle(surf, orc, w, h, upright):
+    """Frames so small that the upper octaves' grids are empty: keypoints, `ori` and descriptors as
+    the oracle's (noise of a seed for which the oracle finds keypoints, all of them in octave 0)."""
+    frames = np.zeros((2, h, surf.align_up(w, 128)), np.uint8)
+    for f, seed in enumerate((2, 3)):
+        frames[f, :, :w] = np.random.default_rng(seed).integers(0, 256, (h, w), dtype=np.uint8)
+    param = surf.make_param(4, 4.0, upright=upright)
+    res = gpu_run(surf, param, frames, w, h)
+    op = orc.make_param(4, 4.0, upright=upright)
+    for f in range(2):
+        o_pts, o_desc, nc = orc.detect(op, frames[f], w, h)
+        assert len(o_pts) >= 1 and res["cand"][f] == nc
+        compare_frame(res["pts"][f], res["desc"][f], o_pts, o_desc, upright)
+
+
 def test_flat_and_tiny_frames(surf):
     """Edge cases: a constant frame yields no keypoints; a tiny frame works."""
     param = surf.make_param(4, 4.0, upright=True)
