@@ -120,6 +120,7 @@ _sigs = {
     "surfhip_run_integral": (_i, [_vp, _vp, _i, _i, _sz]),
     "surfhip_run_hessian": (_i, [_vp, _i]),
     "surfhip_run_describe": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "surfhip_run_nms": (_i, [_vp, _i, _vp, _vp]),
     "surfhip_hessian_bytes_per_frame": (C.c_longlong, [_vp]),
     "surfhip_hessian_plan": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "surfhip_switches_from_env": (C.c_int, [C.c_char_p, C.c_int]),
@@ -390,6 +391,11 @@ class Detector:
         """The describe stage on caller-given points [nframes][max_pts] and device counts, on the
         integral images of the last run_integral / detect_batch (surfhip_run_describe)."""
         check(_lib.surfhip_run_describe(self.h, points_ptr, counts_ptr, nframes, desc_ptr), "run_describe")
+
+    def run_nms(self, nframes, points_ptr, counts_ptr) -> None:
+        """The NMS stage (scan, fit, sort) on the response planes resident in the workspace and the
+        integral images of the last run_integral / detect_batch (surfhip_run_nms)."""
+        check(_lib.surfhip_run_nms(self.h, nframes, points_ptr, counts_ptr), "run_nms")
 
     def candidates(self, nframes: int) -> np.ndarray:
         out = np.zeros(nframes, np.int32)

@@ -753,6 +753,22 @@ int surfhip_run_describe(surfhip_detector* d, surfhip_point* points, const int* 
     return SURFHIP_OK;
 }
 
+// The NMS stage of detect_batch on what is resident: the response planes in d->resp (the caller may have
+// written them through surfhip_detector_workspace) and the integral of the last run_integral / detect_batch.
+// The same launch_nms and launch_sort calls as surfhip_detect_batch_next makes, laplace sign taken in the fit.
+int surfhip_run_nms(surfhip_detector* d, int nframes, surfhip_point* points, int* counts)
+{
+    if (!d || !points || !counts || nframes < 1 || nframes > d->max_batch) return SURFHIP_ERR_INVALID;
+    if (!d->last.frames) return SURFHIP_ERR_INVALID;    // no run_integral / detect_batch yet: no integral
+    hipStream_t s = d->stream;
+    HIPCHK(launch_nms(d->ii, d->resp, nframes, d->P, d->d_oct, d->plan, d->scan_key, d->scan_src, d->scan_cube,
+                      d->item_count, d->item_off, d->cand, d->keys, d->cand_count, d->cap, d->status, s, d->sw,
+                      false));
+    HIPCHK(launch_sort(d->cand, d->keys, d->gscratch, d->cand_count, d->item_off, d->plan.nms_start[kMaxOct] * 4,
+                       d->cap, nframes, points, d->max_pts, counts, d->offsets, d->order, d->status, s, d->sw));
+    return SURFHIP_OK;
+}
+
 // This batch's integral buffer: the one the previous call prefetched into (`have`), else the current
 // one; a fused plan's Hessian writes the integral itself, into buffer 0.  The second buffer is allocated
 // on first use of the pipelined entry point (a plain detect_batch caller never pays for it).

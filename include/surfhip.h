@@ -262,6 +262,22 @@ int surfhip_run_hessian(surfhip_detector* det, int nframes);
 int surfhip_run_describe(surfhip_detector* det, surfhip_point* d_points, const int* d_counts, int nframes,
                          float* d_desc);
 
+/* The NMS stage alone (scan, prefix, fit, sort: findMaximumWithInterp,
+ * surfd.cu:676-832) on what is resident: the response planes in the
+ * detector's workspace (surfhip_detector_workspace's d_resp, frame f at
+ * d_resp + f * resp_stride; the caller may have overwritten them) and the
+ * integral images the last run_integral or detect_batch left
+ * (SURFHIP_ERR_INVALID if there was none), with the launches a detect_batch
+ * of nframes frames without descriptors makes: the laplace sign is taken in
+ * the fit.  Planes 0 / 1 of octaves > 0 are read as views of the previous
+ * octave's planes 2 / 4 at (2r, 2c), never from their own storage, and no
+ * pad column [sw, sp) is read.  d_points[nframes][max_pts] and
+ * d_counts[nframes] are written as detect_batch writes them (canonical
+ * order, min(found, max_pts) per frame).  Asynchronous on the detector's
+ * stream.  surfhip_detector_candidates, surfhip_detector_status and
+ * surfhip_batch_total then answer for this run. */
+int surfhip_run_nms(surfhip_detector* det, int nframes, surfhip_point* d_points, int* d_counts);
+
 /* Algorithmic (compulsory) HBM bytes per frame of the Hessian stage:
  * integral image read once + valid responses written. */
 long long surfhip_hessian_bytes_per_frame(surfhip_detector* det);

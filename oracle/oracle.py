@@ -167,6 +167,27 @@ def hessian(p: Param, img: np.ndarray, w: int, h: int):
     return ii, resp, g, octs
 
 
+def find_points(p: Param, g: Geom, octs, ii: np.ndarray, resp: np.ndarray, max_pts: int = 65536):
+    """or_find_points on given response planes (flat float32 array in the reference layout, planes 0 / 1
+    of octaves > 0 holding their halfImage copies) and integral image: (points[min(n, max_pts)] in
+    canonical order, n = the candidate count before the max_pts cut)."""
+    ii = np.ascontiguousarray(ii, np.int32)
+    resp = np.ascontiguousarray(resp, np.float32)
+    assert resp.size == g.tot_osize and ii.shape == (g.iwhp.y, g.iwhp.z)
+    pts = np.zeros(max_pts, POINT_DTYPE)
+    n = _L.or_find_points(C.byref(p), C.byref(g), octs, ii.ctypes.data, resp.ctypes.data, pts.ctypes.data, max_pts)
+    return pts[:min(n, max_pts)].copy(), n
+
+
+def fit_quadrat(src: np.ndarray, s: int, r: int, c: int, osize: int, sp: int):
+    """or_test_fit (fitQuadrat, surfd.cu:942-988) at (s, r, c) of one octave's planes `src` (flat float32,
+    plane s at s * osize, row pitch sp): (strength, off[3] = (scale, row, column) offsets)."""
+    assert src.dtype == np.float32 and src.flags.c_contiguous
+    off = np.zeros(3, np.float32)
+    st = _L.or_test_fit(src.ctypes.data, off.ctypes.data, s, r, c, osize, sp)
+    return np.float32(st), off
+
+
 def detect(p: Param, img: np.ndarray, w: int, h: int, max_pts: int = 65536, desc: bool = True):
     """or_detect_and_compute: (points[n] structured, descriptors[n, nf] or None, n_candidates)."""
     img = np.ascontiguousarray(img)

@@ -32,6 +32,8 @@ def exported(lib: str, demangle=False):
 def test_surfhip_exports_every_declared_symbol(surf):
     names = declared_functions("surfhip.h")
     assert len(names) >= 40
+    for stage in ("surfhip_run_integral", "surfhip_run_hessian", "surfhip_run_nms", "surfhip_run_describe"):
+        assert stage in names, stage
     syms = exported(os.path.join(PKG, "libsurfhip.so"))
     missing = [n for n in names if not re.search(rf"\bT {n}$", syms, flags=re.M)]
     assert not missing, missing
