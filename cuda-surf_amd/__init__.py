@@ -110,6 +110,8 @@ _sigs = {
     "surfhip_detector_candidates": (_i, [_vp, C.POINTER(_i), _i]),
     "surfhip_detector_status": (_i, [_vp, C.POINTER(_i)]),
     "surfhip_detector_capacity": (_i, [_vp, C.POINTER(_i)]),
+    "surfhip_detector_set_keep": (_i, [_vp, _i, _i]),
+    "surfhip_detector_get_keep": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     "surfhip_detector_set_profiling": (_i, [_vp, _i]),
     "surfhip_detector_stage_times": (_i, [_vp, C.POINTER(C.c_float)]),
     "surfhip_detector_time_hessian": (_i, [_vp, _i]),
@@ -316,6 +318,23 @@ def make_param(noctaves=4, thresh=0.2, doubled=False, init_mask_size=9, sampling
     return p
 
 
+KEEP_FIRST, KEEP_STRONGEST = 0, 1       # Detector.set_keep modes (SURFHIP_KEEP_*)
+
+
+def select_strongest(pts: np.ndarray, n: int) -> np.ndarray:
+    """The indices, ascending, of the points of a canonical-order POINT_DTYPE array (one frame of a dump,
+    a slab or a keep-all result) that KEEP_STRONGEST with budget n keeps.  Strengths are ordered by the
+    order-preserving map of their IEEE bits, m(u) = u ^ (0xffffffff if u >> 31 else 0x80000000): a total
+    order with -0.0 below +0.0 and a defined place for a NaN; of equal strengths the earlier point wins."""
+    if n < 1:
+        raise ValueError("select_strongest: n must be at least 1")
+    u = np.ascontiguousarray(pts["strength"]).view(np.uint32).astype(np.uint64)
+    m = u ^ np.where(u >> np.uint64(31), np.uint64(0xFFFFFFFF), np.uint64(0x80000000))
+    idx = np.arange(len(pts), dtype=np.int64)
+    best = np.lexsort((idx, np.uint64(0xFFFFFFFF) - m))     # strongest first, the earlier index on ties
+    return np.sort(best[:n])
+
+
 class Detector:
     """One geometry + SurfParam + batch scratch on the current device."""
 
@@ -414,6 +433,18 @@ class Detector:
         c = C.c_int()
         check(_lib.surfhip_detector_capacity(self.h, C.byref(c)), "capacity")
         return c.value
+
+    def set_keep(self, mode: int, n: int = 0) -> None:
+        """The per-frame keypoint budget of every later call (surfhip_detector_set_keep): KEEP_FIRST, the
+        first n in canonical order, or KEEP_STRONGEST, the n strongest (selected on the device before
+        describe, returned in canonical order; `select_strongest` restates the rule).  n = 0: max_pts."""
+        check(_lib.surfhip_detector_set_keep(self.h, mode, n), "set_keep")
+
+    def keep(self):
+        """(mode, n) as set_keep left them, n resolved (never 0)."""
+        mode, n = _i(), _i()
+        check(_lib.surfhip_detector_get_keep(self.h, C.byref(mode), C.byref(n)), "get_keep")
+        return mode.value, n.value
 
     def workspace(self):
         ii, iis, rs, rss = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t()

@@ -88,6 +88,7 @@ struct surfhip_detector {
     uint32_t* keys = nullptr;
     uint64_t* gscratch = nullptr;
     int* cand_count = nullptr;
+    KeepRule keep;                      // surfhip_detector_set_keep: (SURFHIP_KEEP_FIRST, max_pts) until set
     uint32_t* scan_key = nullptr;       // NMS survivors awaiting interpolation
     uint32_t* scan_src = nullptr;
     float* scan_cube = nullptr;         // the survivors' fit inputs (kCubeCap per scan item)
@@ -511,7 +512,7 @@ static int derive(surfhip_detector* d)
 static void free_all(surfhip_detector* d)
 {
     void* ptrs[] = {d->d_oct, d->iib[0], d->iib[1], d->resp, d->colsum, d->rowseg, d->psum, d->cand, d->keys, d->gscratch, d->cand_count,
-                    d->scan_key, d->scan_src, d->scan_cube, d->item_count, d->item_off,
+                    d->keep.valid, d->scan_key, d->scan_src, d->scan_cube, d->item_count, d->item_off,
                     d->offsets, d->order, d->pcount, d->work, d->status, d->pts1, d->desc1, d->count1, d->dbl};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -598,6 +599,8 @@ int surfhip_detector_create(surfhip_detector** out, const surfhip_param* param, 
     ALLOC(d->cand, B * d->cap * sizeof(surfhip_point));
     ALLOC(d->keys, B * d->cap * sizeof(uint32_t));
     ALLOC(d->cand_count, B * sizeof(int));
+    d->keep.n = max_pts;
+    ALLOC(d->keep.valid, B * sizeof(int));
     d->nitems = d->plan.nms_start[kMaxOct] * 4;
     ALLOC(d->scan_key, B * (size_t)d->nitems * kItemCap * sizeof(uint32_t));
     ALLOC(d->scan_src, B * (size_t)d->nitems * kItemCap * sizeof(uint32_t));
@@ -765,7 +768,8 @@ int surfhip_run_nms(surfhip_detector* d, int nframes, surfhip_point* points, int
                       d->item_count, d->item_off, d->cand, d->keys, d->cand_count, d->cap, d->status, s, d->sw,
                       false));
     HIPCHK(launch_sort(d->cand, d->keys, d->gscratch, d->cand_count, d->item_off, d->plan.nms_start[kMaxOct] * 4,
-                       d->cap, nframes, points, d->max_pts, counts, d->offsets, d->order, d->status, s, d->sw));
+                       d->cap, nframes, points, d->max_pts, counts, d->offsets, d->order, d->status, s, d->sw,
+                       d->keep));
     return SURFHIP_OK;
 }
 
@@ -937,7 +941,8 @@ int surfhip_detect_batch_next(surfhip_detector* d, const uint8_t* frames, int nf
                       how.trace));
     if (prof) HIPCHK(hipEventRecord(d->ev[3], s));
     HIPCHK(launch_sort(d->cand, d->keys, d->gscratch, d->cand_count, d->item_off, d->plan.nms_start[kMaxOct] * 4,
-                       d->cap, nframes, points, d->max_pts, counts, d->offsets, d->order, d->status, s, d->sw));
+                       d->cap, nframes, points, d->max_pts, counts, d->offsets, d->order, d->status, s, d->sw,
+                       d->keep));
     if (prof) HIPCHK(hipEventRecord(d->ev[4], s));
     if (pf == kPrefDescribe) HIPCHK(prefetch_next(d, next, s));
     if (d->desc_ev) HIPCHK(hipEventRecord(d->desc_ev, s));
@@ -1015,6 +1020,23 @@ int surfhip_detector_status(surfhip_detector* d, int* truncated)
     HIPCHK(hipMemcpyAsync(&st, d->status, sizeof(int), hipMemcpyDeviceToHost, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
     *truncated = st & 1;
+    return SURFHIP_OK;
+}
+
+int surfhip_detector_set_keep(surfhip_detector* d, int mode, int n)
+{
+    if (!d || (mode != SURFHIP_KEEP_FIRST && mode != SURFHIP_KEEP_STRONGEST) || n < 0 || n > d->max_pts)
+        return SURFHIP_ERR_INVALID;
+    d->keep.mode = mode;
+    d->keep.n = n ? n : d->max_pts;
+    return SURFHIP_OK;
+}
+
+int surfhip_detector_get_keep(surfhip_detector* d, int* mode, int* n)
+{
+    if (!d || !mode || !n) return SURFHIP_ERR_INVALID;
+    *mode = d->keep.mode;
+    *n = d->keep.n;
     return SURFHIP_OK;
 }
 

@@ -199,10 +199,19 @@ hipError_t launch_nms(const int32_t* ii, const float* resp, int nframes, const F
                       const OctaveParams* d_oct, const LaunchPlan& plan, uint32_t* scan_key, uint32_t* scan_src,
                       float* scan_cube, int* item_count, int* item_off, surfhip_point* cand, uint32_t* keys,
                       int* cand_count, int cap, int* status, hipStream_t s, const Switches& sw, bool stash_trace);
-hipError_t launch_sort(const surfhip_point* cand, const uint32_t* keys, uint64_t* gscratch,
+// The per-frame keypoint budget (surfhip_detector_set_keep): at most n (1 .. max_pts) points per frame, the
+// first n in canonical order or the n strongest.  valid: max_batch ints of device scratch, each frame's valid
+// candidates before k_keep_strongest's selection (SURFHIP_KEEP_STRONGEST only).
+struct KeepRule {
+    int mode = SURFHIP_KEEP_FIRST;
+    int n = 0;
+    int* valid = nullptr;
+};
+// (SURFHIP_KEEP_STRONGEST writes kNoKey over the keys of the candidates it drops)
+hipError_t launch_sort(const surfhip_point* cand, uint32_t* keys, uint64_t* gscratch,
                        const int* cand_count, const int* soff, int items_per_frame, int cap, int nframes,
                        surfhip_point* out, int max_pts, int* out_count, int* offsets, int* order, int* status,
-                       hipStream_t s, const Switches& sw);
+                       hipStream_t s, const Switches& sw, const KeepRule& keep);
 hipError_t set_max_lds(const void* fn, int bytes);
 // The describe kernel of a batch of nframes and where its laplace sign is
 // taken, chosen once per call (surfhip_detect_batch_next).  kDescU2: upright

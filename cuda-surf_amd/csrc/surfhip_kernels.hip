@@ -15,7 +15,8 @@
 //   halfImage                  surfd.cu:321-331            -> surfhip_nms.inc -> virtual planes (OctView)
 //   findMaximumWithInterp      surfd.cu:676-832, 3058-3079 -> surfhip_nms.inc -> k_nms_scan, k_scan_*, k_nms_fit
 //   (atomicInc emission order) surfd.cu:825-830            -> surfhip_sort.inc -> k_sort / k_sort_rank (canonical
-//                              order + max_pts cap), k_offsets
+//                              order + per-frame cap), k_offsets; surfhip_keep.inc -> k_keep_strongest (the
+//                              n strongest of a frame ahead of the sort: surfhip_detector_set_keep)
 //   assignOrientationApprox    surfd.cu:1711-1960          -> surfhip_desc.inc -> orientation_wave in k_describe,
 //                              k_describe_rot
 //   describe*WithoutNormalization + normalize
@@ -666,6 +667,7 @@ hipError_t launch_hess_ii(const HessianArgs& a, hipStream_t s)
 }
 
 #include "surfhip_nms.inc"
+#include "surfhip_keep.inc"
 #include "surfhip_sort.inc"
 #include "surfhip_desc.inc"
 #include "surfhip_desc_ur.inc"

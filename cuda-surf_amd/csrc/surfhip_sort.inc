@@ -1,6 +1,6 @@
-// surfhip_sort.inc -- canonical keypoint order, the max_pts cap and the describe
+// surfhip_sort.inc -- canonical keypoint order, the per-frame cap and the describe
 // schedule (k_sort, k_sort_rank, k_offsets; launch_sort).  Included by
-// surfhip_kernels.hip.
+// surfhip_kernels.hip after surfhip_keep.inc.
 
 // ======================================================================
 // Canonical order + max_pts cap.  The reference emits in atomicInc order
@@ -145,7 +145,8 @@ __global__ __launch_bounds__(1024) void k_sort(const surfhip_point* __restrict__
                                                uint64_t* __restrict__ gscratch, const int* __restrict__ cand_count,
                                                const int* __restrict__ soff, int items_per_frame, int cap,
                                                surfhip_point* __restrict__ out, int max_pts,
-                                               int* __restrict__ out_count, int* __restrict__ order, int* status)
+                                               int* __restrict__ out_count, int* __restrict__ order, int* status,
+                                               int keep_n, const int* __restrict__ pre_valid)
 {
     extern __shared__ __attribute__((aligned(16))) uint64_t sk[];
     __shared__ int nvalid;
@@ -170,9 +171,10 @@ __global__ __launch_bounds__(1024) void k_sort(const surfhip_point* __restrict__
     else if (in_lds && blockDim.x == 1024) bitonic_sort_lds(s, n);
     else bitonic_sort(s, n);
     const int valid = nvalid;
-    // accepted candidates beyond the cap were dropped: report it
-    if (threadIdx.x == 0 && cand_count[f] > valid) atomicOr(status, 1);
-    const int keep = min(valid, max_pts);
+    // accepted candidates beyond the cap were dropped: report it (pre_valid:
+    // k_keep_strongest ran, the frame's valid count from before its selection)
+    if (threadIdx.x == 0 && cand_count[f] > (pre_valid ? pre_valid[f] : valid)) atomicOr(status, 1);
+    const int keep = min(valid, keep_n);        // the per-frame budget (<= max_pts, the slot stride)
     for (int t = threadIdx.x; t < keep; t += blockDim.x)
         out[(size_t)f * max_pts + t] = cand[(size_t)f * cap + (uint32_t)(s[t] & 0xffffffffu)];
     if (threadIdx.x == 0) out_count[f] = keep;
@@ -238,7 +240,8 @@ __global__ __launch_bounds__(256) void k_sort_rank(const surfhip_point* __restri
                                                    const int* __restrict__ soff, int items_per_frame, int cap,
                                                    int wgs_per_frame, surfhip_point* __restrict__ out, int max_pts,
                                                    int* __restrict__ out_count, int* __restrict__ order,
-                                                   int* __restrict__ status)
+                                                   int* __restrict__ status, int keep_n,
+                                                   const int* __restrict__ pre_valid)
 {
     __shared__ __attribute__((aligned(16))) uint32_t sk[kRankLds];
     __shared__ int nvalid;
@@ -267,10 +270,10 @@ __global__ __launch_bounds__(256) void k_sort_rank(const surfhip_point* __restri
     if (mine) atomicAdd(&nvalid, mine);
     __syncthreads();
     const int valid = nvalid;
-    const int keep = min(valid, max_pts);
+    const int keep = min(valid, keep_n);        // the per-frame budget (<= max_pts, the slot stride)
     if (r == 0 && threadIdx.x == 0) {
         out_count[f] = keep;
-        if (cand_count[f] > valid) atomicOr(status, 1);
+        if (cand_count[f] > (pre_valid ? pre_valid[f] : valid)) atomicOr(status, 1);
     }
     const int part = (int)(threadIdx.x & (kRankT - 1));
     // candidate groups r, r + wgs, ...: a dense frame (cnt up to the cap)
@@ -334,24 +337,35 @@ __global__ __launch_bounds__(1024) void k_offsets(const int* __restrict__ counts
         if (b + i < nframes) { offsets[b + i] = run; run += counts[b + i]; }
 }
 
-hipError_t launch_sort(const surfhip_point* cand, const uint32_t* keys, uint64_t* gscratch,
+hipError_t launch_sort(const surfhip_point* cand, uint32_t* keys, uint64_t* gscratch,
                        const int* cand_count, const int* soff, int items_per_frame, int cap, int nframes,
                        surfhip_point* out, int max_pts, int* out_count, int* offsets, int* order, int* status,
-                       hipStream_t s, const Switches& sw)
+                       hipStream_t s, const Switches& sw, const KeepRule& keep)
 {
+    // SURFHIP_KEEP_STRONGEST: the losers' keys become kNoKey ahead of the sort
+    // (SURFHIP_KEEP_FIRST is the sort kernels' own cut at keep.n)
+    const int* pre_valid = nullptr;
+    if (keep.mode == SURFHIP_KEEP_STRONGEST) {
+        const int slots = std::min(cap, kSortCap);
+        hipError_t e = set_max_lds(reinterpret_cast<const void*>(&k_keep_strongest), (int)(kSortCap * sizeof(uint64_t)));
+        if (e != hipSuccess) return e;
+        k_keep_strongest<<<nframes, 1024, slots * sizeof(uint64_t), s>>>(cand, keys, soff, items_per_frame, cap, slots,
+                                                                         keep.n, keep.valid);
+        pre_valid = keep.valid;
+    }
     if (nframes <= kRankBatch && !sw.sort_bitonic) {
         // workgroups per frame: one per 16 candidates up to 256 (~3,000
         // candidates of a 1080p frame: 188), beyond that each takes several
         // groups of 16 with the keys it staged once
         const int per = std::min((cap + 256 / kRankT - 1) / (256 / kRankT), kRankMaxWgs);
         k_sort_rank<<<nframes * per, 256, 0, s>>>(cand, keys, cand_count, soff, items_per_frame, cap, per, out,
-                                                  max_pts, out_count, order, status);
+                                                  max_pts, out_count, order, status, keep.n, pre_valid);
     } else {
         hipError_t e = set_max_lds(reinterpret_cast<const void*>(&k_sort), (int)(kSortCap * sizeof(uint64_t)));
         if (e != hipSuccess) return e;
         k_sort<<<nframes, 1024, kSortCap * sizeof(uint64_t), s>>>(cand, keys, gscratch, cand_count, soff,
                                                                   items_per_frame, cap, out, max_pts, out_count,
-                                                                  order, status);
+                                                                  order, status, keep.n, pre_valid);
     }
     k_offsets<<<1, 1024, 0, s>>>(out_count, nframes, offsets);
     return hipGetLastError();

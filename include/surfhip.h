@@ -205,6 +205,34 @@ int surfhip_detector_candidates(surfhip_detector* det, int* h_counts, int nframe
 int surfhip_detector_status(surfhip_detector* det, int* truncated);
 int surfhip_detector_capacity(surfhip_detector* det, int* cand_cap);
 
+/* The per-frame keypoint budget: which points of a frame are kept when it
+ * holds more than n.  The candidates considered are the frame's valid ones
+ * among its first cand_cap NMS survivors in scan order; the kept points are
+ * always written in canonical order and the count is min(valid, n).
+ *   SURFHIP_KEEP_FIRST      the first n in canonical order (octave 0 first).
+ *   SURFHIP_KEEP_STRONGEST  the n strongest, selected on the device between
+ *       the fit and the sort, before anything is described.  Strengths are
+ *       ordered by m(u) = u ^ ((u >> 31) ? 0xffffffff : 0x80000000) of their
+ *       IEEE bits (a total order: -0.0 below +0.0, a NaN has its place);
+ *       candidate a beats b when m(a.strength) > m(b.strength), or when they
+ *       are equal and a is the earlier in canonical order.  The result is the
+ *       same bits from run to run and at every position of a batch.
+ * n: 0 = max_pts, else 1 .. max_pts.  SURFHIP_ERR_INVALID for any other n, an
+ * unknown mode or a NULL detector (the setting stays as it was).  Host state
+ * only (no GPU call, no synchronisation): it applies to every later
+ * detect_batch, detect_batch_next, detect, run_nms and ingest submit of the
+ * detector and may be changed between calls.  A new detector is
+ * (SURFHIP_KEEP_FIRST, max_pts); get_keep reports the resolved n, never 0.
+ * Slot strides (d_points, d_desc, slabs) stay max_pts whatever n is; laplace,
+ * ori, descriptors, offsets, surfhip_batch_total and the pack functions
+ * follow the kept set.  Dropping points by n never sets `truncated`
+ * (surfhip_detector_status), and surfhip_detector_candidates keeps returning
+ * the raw counts: candidates[f] - counts[f] points of frame f were dropped. */
+#define SURFHIP_KEEP_FIRST     0
+#define SURFHIP_KEEP_STRONGEST 1
+int surfhip_detector_set_keep(surfhip_detector* det, int mode, int n);
+int surfhip_detector_get_keep(surfhip_detector* det, int* mode, int* n);
+
 /* Stage timing (HIP events on the detector's stream) for the last
  * detect_batch: ms[0..5] = integral, hessian, nms, sort, describe, total. */
 #define SURFHIP_NSTAGE 6
