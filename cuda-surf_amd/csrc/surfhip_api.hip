@@ -15,6 +15,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <vector>
 
 #include "surfhip.h"
 #include "surfhip_internal.h"
@@ -50,7 +51,20 @@ static inline int align_up(int a, int b) { return (a % b != 0) ? (a - a % b + b)
 enum HessSched { kFused, kIntegralFirst, kSideStream };
 enum Prefetch { kPrefNone, kPrefNms, kPrefDescribe };
 
+// The detector's device memory: a buffer is named once, where it is allocated, and is freed with the detector
+struct DeviceBuffers {
+    std::vector<void*> owned;
+    template <class T> hipError_t alloc(T*& ptr, size_t bytes)
+    {
+        const hipError_t e = hipMalloc((void**)&ptr, bytes);
+        if (e == hipSuccess) owned.push_back(ptr);
+        return e;
+    }
+    ~DeviceBuffers() { for (void* p : owned) (void)hipFree(p); }
+};
+
 struct surfhip_detector {
+    DeviceBuffers mem;
     int dev = 0;
     int cus = 256;                      // compute units of dev (the describe kernels' persistent grid)
     hipStream_t stream = nullptr;
@@ -61,7 +75,7 @@ struct surfhip_detector {
     OctaveParams* d_oct = nullptr;      // device copy read by the fused launches
     LaunchPlan plan{};
     HessSched sched = kFused;
-    int W = 0, H = 0, max_batch = 0, max_pts = 0, cap = 0;   // W x H: the frames the integral is taken of
+    int W = 0, H = 0, max_batch = 0, max_pts = 0;   // W x H: the frames the integral is taken of
     int srcW = 0, srcH = 0;             // the caller's frames (= W x H unless doubled)
     uint8_t* dbl = nullptr;             // doubled: the (2 srcW - 2) x (2 srcH - 2) frames D
     int dpitch = 0;
@@ -84,22 +98,10 @@ struct surfhip_detector {
     // plan.rsum: k_hess_p0's per-strip row sums of the batch, which
     // k_rowsum_p0 adds up into rowseg (no k_ii_rowseg pass, no prefetch)
     uint32_t* psum = nullptr;
-    surfhip_point* cand = nullptr;
-    uint32_t* keys = nullptr;
-    uint64_t* gscratch = nullptr;
-    int* cand_count = nullptr;
+    Candidates cands{};                 // launch_nms -> launch_sort
     KeepRule keep;                      // surfhip_detector_set_keep: (SURFHIP_KEEP_FIRST, max_pts) until set
-    uint32_t* scan_key = nullptr;       // NMS survivors awaiting interpolation
-    uint32_t* scan_src = nullptr;
-    float* scan_cube = nullptr;         // the survivors' fit inputs (kCubeCap per scan item)
-    int* item_count = nullptr;          // survivors per NMS scan item
-    int* item_off = nullptr;            // their exclusive prefix (+ total)
-    int nitems = 0;                     // scan items per frame
-    int* offsets = nullptr;
-    int* order = nullptr;               // per frame: keypoint indices in row order (describe schedule)
+    DescribeSchedule schedule{};        // launch_sort / launch_plant -> launch_describe, launch_pack
     int* pcount = nullptr;              // surfhip_run_describe: the caller's counts cut to [0, max_pts]
-    float4* work = nullptr;             // the describe schedule flattened: kWorkF4 float4 per keypoint (k_worklist)
-    int* status = nullptr;
     // single-frame API slots
     surfhip_point* pts1 = nullptr;
     float* desc1 = nullptr;
@@ -118,6 +120,18 @@ struct surfhip_detector {
     int hev_n = 0;
     FrameBatch last;                    // u8 source of the last integral (surfhip_run_hessian)
     long long hess_bytes = 0;
+
+    ~surfhip_detector()                 // (then mem's buffers)
+    {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        for (auto& batch : hev)
+            for (hipEvent_t e : batch)
+                if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {fork, fork2, join})
+            if (e) (void)hipEventDestroy(e);
+        if (side) (void)hipStreamDestroy(side);
+    }
 };
 
 // t into buf[len], cut to fit and NUL-terminated; returns the full length
@@ -509,22 +523,81 @@ static int derive(surfhip_detector* d)
     return SURFHIP_OK;
 }
 
-static void free_all(surfhip_detector* d)
+// A derived detector's plan and what it owns on the device (a failure's leftovers go with the detector)
+static hipError_t create_device_state(surfhip_detector* d)
 {
-    void* ptrs[] = {d->d_oct, d->iib[0], d->iib[1], d->resp, d->colsum, d->rowseg, d->psum, d->cand, d->keys, d->gscratch, d->cand_count,
-                    d->keep.valid, d->scan_key, d->scan_src, d->scan_cube, d->item_count, d->item_off,
-                    d->offsets, d->order, d->pcount, d->work, d->status, d->pts1, d->desc1, d->count1, d->dbl};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    for (int i = 0; i < SURFHIP_NSTAGE; i++)
-        if (d->ev[i]) (void)hipEventDestroy(d->ev[i]);
-    for (int i = 0; i < SURFHIP_MAX_HESS_EV; i++)
-        for (int j = 0; j < 3; j++)
-            if (d->hev[i][j]) (void)hipEventDestroy(d->hev[i][j]);
-    if (d->fork) (void)hipEventDestroy(d->fork);
-    if (d->fork2) (void)hipEventDestroy(d->fork2);
-    if (d->join) (void)hipEventDestroy(d->join);
-    if (d->side) (void)hipStreamDestroy(d->side);
+    const size_t B = (size_t)d->max_batch, max_pts = (size_t)d->max_pts;
+    Candidates& c = d->cands;
+    hipError_t e = hipSuccess;
+    auto alloc = [&](auto*& ptr, size_t bytes) {        // (nothing more after a failure)
+        if (e == hipSuccess) e = d->mem.alloc(ptr, bytes);
+    };
+    d->CW = (d->W + 1 <= 2048) ? 2048 : (d->W + 1 <= 4096 ? 4096 : 8192);
+    make_plan(d->P, d->oct, d->sw, d->plan, d->max_batch);
+    // the u8 kernels write the integral image: one stream; no kernel reads the u8 frames: integral first, one
+    // stream; else: u8 kernels on the detector stream, the integral and the integral-image kernels beside them
+    d->sched = d->plan.iiw ? kFused : !plan_reads_frames(d->plan) ? kIntegralFirst : kSideStream;
+    const size_t rowseg_bytes = B * d->plan.rs_nstrips * d->plan.rs_rows * sizeof(uint32_t);
+    if (d->plan.iiw) {
+        // the stage also writes the integral image (read: the u8 frame)
+        d->hess_bytes += (long long)d->W * d->H;
+        alloc(d->rowseg, rowseg_bytes);
+        if (d->plan.rsum) alloc(d->psum, B * d->plan.q0_strips * d->plan.rs_rows * sizeof(uint32_t));
+    }
+    alloc(d->d_oct, sizeof(OctaveParams) * kMaxOct);
+    alloc(d->iib[0], B * d->P.ii_stride * sizeof(int32_t));
+    d->ii = d->iib[0];
+    alloc(d->resp, B * d->tot_osize * sizeof(float));
+    alloc(d->colsum, (size_t)integral_bands(d->H, d->max_batch, d->sw) * d->CW * sizeof(uint32_t));
+    alloc(c.cand, B * c.cap * sizeof(surfhip_point));
+    alloc(c.keys, B * c.cap * sizeof(uint32_t));
+    alloc(c.cand_count, B * sizeof(int));
+    d->keep.n = d->max_pts;
+    alloc(d->keep.valid, B * sizeof(int));
+    const size_t items = B * (size_t)scan_items(d->plan);
+    alloc(c.scan_key, items * kItemCap * sizeof(uint32_t));
+    alloc(c.scan_src, items * kItemCap * sizeof(uint32_t));
+    alloc(c.scan_cube, items * kCubeCap * kCubeF * sizeof(float));
+    alloc(c.item_count, items * sizeof(int));
+    alloc(c.item_off, (2 * items + 64) * sizeof(int));
+    alloc(d->schedule.offsets, (B + 1) * sizeof(int));
+    alloc(d->schedule.order, B * max_pts * sizeof(int));
+    alloc(d->pcount, B * sizeof(int));
+    alloc(d->schedule.work, B * max_pts * kWorkF4 * sizeof(float4));
+    alloc(c.status, 256 + kDescQueueBytes);
+    d->schedule.queue = c.status + 64;
+    alloc(d->pts1, max_pts * sizeof(surfhip_point));
+    alloc(d->desc1, max_pts * d->param.nfeatures * sizeof(float));
+    alloc(d->count1, 16);
+    if (c.cap > kSortCap) alloc(c.gscratch, B * c.cap * sizeof(uint64_t));
+    if (d->param.doubled) {
+        d->dpitch = align_up(d->W, 128);
+        d->dstride = (long long)d->H * d->dpitch;
+        alloc(d->dbl, B * (size_t)d->dstride);
+    }
+    // zero once: integral pad columns and response pad columns are never
+    // written by the kernels and never read by them either
+    if (e == hipSuccess) e = hipMemcpy(d->d_oct, d->oct, sizeof(OctaveParams) * kMaxOct, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(d->iib[0], 0, B * d->P.ii_stride * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemset(d->resp, 0, B * d->tot_osize * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(c.status, 0, 16);
+    // strip 0's slab and the rows past H stay zero (k_ii_rowseg never writes them)
+    if (e == hipSuccess && d->rowseg) e = hipMemset(d->rowseg, 0, rowseg_bytes);
+    if (e != hipSuccess) return e;
+    // LUTs (surf.cpp:358-371) and orientation bins (surf.cpp:83-89); the
+    // values are geometry-independent, so one constant table serves all
+    Tables t;
+    for (int n = 0; n < 83; n++) t.lut1[n] = expf(-(n + 0.5f) / 12.5f);
+    for (int n = 0; n < 40; n++) t.lut2[n] = expf(-(n + 0.5f) / 8.f);
+    t.bins[0] = (float)(-3.14159265358979323846);
+    for (int i = 1; i < 72; i++) t.bins[i] = t.bins[i - 1] + 0.08726646259971647f;
+    e = set_tables(t);
+    for (int i = 0; i < SURFHIP_NSTAGE && e == hipSuccess; i++) e = hipEventCreate(&d->ev[i]);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&d->side, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&d->fork, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&d->join, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&d->fork2, hipEventDisableTiming);
+    return e;
 }
 
 int surfhip_detector_create(surfhip_detector** out, const surfhip_param* param, int width, int height,
@@ -537,25 +610,22 @@ int surfhip_detector_create(surfhip_detector** out, const surfhip_param* param, 
                                 param->doubled ? param->sampling / 2 : param->sampling, param->upright,
                                 param->extend, param->desc_wsz);
     if (rc != SURFHIP_OK) return rc;
+    // doubled (surf.cpp:234-235, 377-378): the integral is taken of the
+    // (2W-2) x (2H-2) upsampled frames D, giving the (2W-1) x (2H-1) grid
+    const int W = chk.doubled ? 2 * width - 2 : width;
+    if (W + 1 > 8192) return SURFHIP_ERR_UNSUPPORTED;
     surfhip_detector* d = new surfhip_detector();
     d->sw = read_switches();
     d->param = chk;
     d->srcW = width;
     d->srcH = height;
-    // doubled (surf.cpp:234-235, 377-378): the integral is taken of the
-    // (2W-2) x (2H-2) upsampled frames D, giving the (2W-1) x (2H-1) grid
-    d->W = chk.doubled ? 2 * width - 2 : width;
+    d->W = W;
     d->H = chk.doubled ? 2 * height - 2 : height;
-    if (d->W + 1 > 8192) {
-        delete d;
-        return SURFHIP_ERR_UNSUPPORTED;
-    }
     d->max_batch = max_batch;
     d->max_pts = max_pts;
-    int cap = cand_cap > 0 ? cand_cap : std::max(max_pts, kSortCap);
-    int c2 = 1;
-    while (c2 < cap) c2 <<= 1;
-    d->cap = c2;
+    const int cap = cand_cap > 0 ? cand_cap : std::max(max_pts, kSortCap);
+    d->cands.cap = 1;
+    while (d->cands.cap < cap) d->cands.cap <<= 1;
     d->stream = (hipStream_t)stream;
     hipError_t e = hipGetDevice(&d->dev);
     if (e == hipSuccess) {
@@ -569,97 +639,15 @@ int surfhip_detector_create(surfhip_detector** out, const surfhip_param* param, 
     // the largest octave, so its extent bounds them all
     if (rc == SURFHIP_OK && (d->oct[0].sh >= 16384 || d->oct[0].sw >= 16384 || d->oct[0].nms_gy >= 8192))
         rc = SURFHIP_ERR_UNSUPPORTED;
+    if (rc == SURFHIP_OK && (e = create_device_state(d)) != hipSuccess)
+        rc = e == hipErrorOutOfMemory ? SURFHIP_ERR_NOMEM : SURFHIP_ERR_HIP;
     if (rc != SURFHIP_OK) {
         if (e != hipSuccess) g_last_hip = e;
         delete d;
         return rc;
     }
-    d->CW = (d->W + 1 <= 2048) ? 2048 : (d->W + 1 <= 4096 ? 4096 : 8192);
-    const size_t B = (size_t)max_batch;
-#define ALLOC(ptr, bytes)                                    \
-    do {                                                     \
-        e = hipMalloc((void**)&(ptr), (bytes));              \
-        if (e != hipSuccess) goto fail;                      \
-    } while (0)
-    make_plan(d->P, d->oct, d->sw, d->plan, max_batch);
-    // the u8 kernels write the integral image: one stream; no kernel reads the u8 frames: integral first, one
-    // stream; else: u8 kernels on the detector stream, the integral and the integral-image kernels beside them
-    d->sched = d->plan.iiw ? kFused : !plan_reads_frames(d->plan) ? kIntegralFirst : kSideStream;
-    if (d->plan.iiw) {
-        // the stage also writes the integral image (read: the u8 frame)
-        d->hess_bytes += (long long)d->W * d->H;
-        ALLOC(d->rowseg, B * d->plan.rs_nstrips * d->plan.rs_rows * sizeof(uint32_t));
-        if (d->plan.rsum) ALLOC(d->psum, B * d->plan.q0_strips * d->plan.rs_rows * sizeof(uint32_t));
-    }
-    ALLOC(d->d_oct, sizeof(OctaveParams) * kMaxOct);
-    ALLOC(d->iib[0], B * d->P.ii_stride * sizeof(int32_t));
-    d->ii = d->iib[0];
-    ALLOC(d->resp, B * d->tot_osize * sizeof(float));
-    ALLOC(d->colsum, (size_t)integral_bands(d->H, max_batch, d->sw) * d->CW * sizeof(uint32_t));
-    ALLOC(d->cand, B * d->cap * sizeof(surfhip_point));
-    ALLOC(d->keys, B * d->cap * sizeof(uint32_t));
-    ALLOC(d->cand_count, B * sizeof(int));
-    d->keep.n = max_pts;
-    ALLOC(d->keep.valid, B * sizeof(int));
-    d->nitems = d->plan.nms_start[kMaxOct] * 4;
-    ALLOC(d->scan_key, B * (size_t)d->nitems * kItemCap * sizeof(uint32_t));
-    ALLOC(d->scan_src, B * (size_t)d->nitems * kItemCap * sizeof(uint32_t));
-    ALLOC(d->scan_cube, B * (size_t)d->nitems * kCubeCap * kCubeF * sizeof(float));
-    ALLOC(d->item_count, B * (size_t)d->nitems * sizeof(int));
-    // prefix (nitems + 1) followed by the scan's per-chunk totals
-    ALLOC(d->item_off, (2 * B * (size_t)d->nitems + 64) * sizeof(int));
-    ALLOC(d->offsets, (B + 1) * sizeof(int));
-    ALLOC(d->order, B * (size_t)max_pts * sizeof(int));
-    ALLOC(d->pcount, B * sizeof(int));
-    ALLOC(d->work, B * (size_t)max_pts * kWorkF4 * sizeof(float4));
-    ALLOC(d->status, 256 + kDescQueueBytes);    // [0]: flags; from [64]: describe work queues
-    ALLOC(d->pts1, (size_t)max_pts * sizeof(surfhip_point));
-    ALLOC(d->desc1, (size_t)max_pts * d->param.nfeatures * sizeof(float));
-    ALLOC(d->count1, 16);
-    if (d->cap > kSortCap) ALLOC(d->gscratch, B * d->cap * sizeof(uint64_t));
-    if (d->param.doubled) {
-        d->dpitch = align_up(d->W, 128);
-        d->dstride = (long long)d->H * d->dpitch;
-        ALLOC(d->dbl, B * (size_t)d->dstride);
-    }
-#undef ALLOC
-    // zero once: integral pad columns and response pad columns are never
-    // written by the kernels and never read by them either
-    e = hipMemcpy(d->d_oct, d->oct, sizeof(OctaveParams) * kMaxOct, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(d->iib[0], 0, B * d->P.ii_stride * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemset(d->resp, 0, B * d->tot_osize * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(d->status, 0, 16);
-    // strip 0's slab and the rows past H stay zero (k_ii_rowseg never writes them)
-    if (e == hipSuccess && d->rowseg)
-        e = hipMemset(d->rowseg, 0, B * d->plan.rs_nstrips * d->plan.rs_rows * sizeof(uint32_t));
-    if (e != hipSuccess) goto fail;
-    {
-        // LUTs (surf.cpp:358-371) and orientation bins (surf.cpp:83-89); the
-        // values are geometry-independent, so one constant table serves all
-        Tables t;
-        for (int n = 0; n < 83; n++) t.lut1[n] = expf(-(n + 0.5f) / 12.5f);
-        for (int n = 0; n < 40; n++) t.lut2[n] = expf(-(n + 0.5f) / 8.f);
-        t.bins[0] = (float)(-3.14159265358979323846);
-        for (int i = 1; i < 72; i++) t.bins[i] = t.bins[i - 1] + 0.08726646259971647f;
-        e = set_tables(t);
-        if (e != hipSuccess) goto fail;
-    }
-    for (int i = 0; i < SURFHIP_NSTAGE; i++) {
-        e = hipEventCreate(&d->ev[i]);
-        if (e != hipSuccess) goto fail;
-    }
-    e = hipStreamCreateWithFlags(&d->side, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&d->fork, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&d->join, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&d->fork2, hipEventDisableTiming);
-    if (e != hipSuccess) goto fail;
     *out = d;
     return SURFHIP_OK;
-fail:
-    g_last_hip = e;
-    free_all(d);
-    delete d;
-    return e == hipErrorOutOfMemory ? SURFHIP_ERR_NOMEM : SURFHIP_ERR_HIP;
 }
 
 int surfhip_detector_destroy(surfhip_detector* d)
@@ -667,7 +655,6 @@ int surfhip_detector_destroy(surfhip_detector* d)
     if (!d) return SURFHIP_ERR_INVALID;
     (void)hipStreamSynchronize(d->stream);
     if (d->side) (void)hipStreamSynchronize(d->side);    // a next-batch integral may still run there
-    free_all(d);
     delete d;
     return SURFHIP_OK;
 }
@@ -750,25 +737,23 @@ int surfhip_run_describe(surfhip_detector* d, surfhip_point* points, const int* 
     if (!d->last.frames) return SURFHIP_ERR_INVALID;    // no run_integral / detect_batch yet: no integral
     DescribeChoice how = choose_describe(d->sw, d->P, nframes);
     how.trace = false;
-    HIPCHK(launch_plant(counts, nframes, d->max_pts, d->pcount, d->offsets, d->order, d->stream));
-    HIPCHK(launch_describe(d->ii, d->P, points, d->max_pts, d->pcount, d->offsets, d->order, d->work, nframes, desc,
-                           d->status + 64, d->stream, false, d->cus, d->sw, how));
+    const PointSlots slots{points, d->max_pts, d->pcount};
+    HIPCHK(launch_plant(counts, nframes, slots, d->schedule, d->stream));
+    HIPCHK(launch_describe(d->ii, d->P, slots, d->schedule, nframes, desc, d->stream, false, d->cus, d->sw, how));
     return SURFHIP_OK;
 }
 
 // The NMS stage of detect_batch on what is resident: the response planes in d->resp (the caller may have
 // written them through surfhip_detector_workspace) and the integral of the last run_integral / detect_batch.
-// The same launch_nms and launch_sort calls as surfhip_detect_batch_next makes, laplace sign taken in the fit.
+// launch_nms and launch_sort on the detector's blocks, as in surfhip_detect_batch_next; laplace sign in the fit.
 int surfhip_run_nms(surfhip_detector* d, int nframes, surfhip_point* points, int* counts)
 {
     if (!d || !points || !counts || nframes < 1 || nframes > d->max_batch) return SURFHIP_ERR_INVALID;
     if (!d->last.frames) return SURFHIP_ERR_INVALID;    // no run_integral / detect_batch yet: no integral
-    hipStream_t s = d->stream;
-    HIPCHK(launch_nms(d->ii, d->resp, nframes, d->P, d->d_oct, d->plan, d->scan_key, d->scan_src, d->scan_cube,
-                      d->item_count, d->item_off, d->cand, d->keys, d->cand_count, d->cap, d->status, s, d->sw,
-                      false));
-    HIPCHK(launch_sort(d->cand, d->keys, d->gscratch, d->cand_count, d->item_off, d->plan.nms_start[kMaxOct] * 4,
-                       d->cap, nframes, points, d->max_pts, counts, d->offsets, d->order, d->status, s, d->sw,
+    FrameBatch b = d->last;
+    b.n = nframes;
+    HIPCHK(launch_nms(hessian_args(d, b), d->cands, d->stream, d->sw, false));
+    HIPCHK(launch_sort(d->cands, d->plan, nframes, {points, d->max_pts, counts}, d->schedule, d->stream, d->sw,
                        d->keep));
     return SURFHIP_OK;
 }
@@ -780,7 +765,7 @@ static hipError_t pick_integral(surfhip_detector* d, bool have, bool pipe)
 {
     if (pipe && d->sched != kFused && !d->iib[1]) {
         const size_t bytes = (size_t)d->max_batch * d->P.ii_stride * sizeof(int32_t);
-        hipError_t e = hipMalloc((void**)&d->iib[1], bytes);
+        hipError_t e = d->mem.alloc(d->iib[1], bytes);
         if (e == hipSuccess) e = hipMemset(d->iib[1], 0, bytes);     // pad columns stay 0
         if (e != hipSuccess) return e;
     }
@@ -928,7 +913,8 @@ int surfhip_detect_batch_next(surfhip_detector* d, const uint8_t* frames, int nf
         HIPCHK(hipEventRecord(d->ev[0], s));
     }
     HIPCHK(source_frames(d, b, s));
-    rc = hessian_stage(d, hessian_args(d, b), have);
+    const HessianArgs a = hessian_args(d, b);
+    rc = hessian_stage(d, a, have);
     if (rc) return rc;
     if (pf == kPrefNms) HIPCHK(prefetch_next(d, next, s));
     // the describe kernel, and getTrace in k_describe_u2 (its integral rows
@@ -936,19 +922,16 @@ int surfhip_detect_batch_next(surfhip_detector* d, const uint8_t* frames, int nf
     // survivor from HBM); no describe: the fit takes it
     DescribeChoice how = choose_describe(d->sw, d->P, nframes);
     if (!desc) how.trace = false;
-    HIPCHK(launch_nms(d->ii, d->resp, nframes, d->P, d->d_oct, d->plan, d->scan_key, d->scan_src, d->scan_cube,
-                      d->item_count, d->item_off, d->cand, d->keys, d->cand_count, d->cap, d->status, s, d->sw,
-                      how.trace));
+    const PointSlots slots{points, d->max_pts, counts};
+    HIPCHK(launch_nms(a, d->cands, s, d->sw, how.trace));
     if (prof) HIPCHK(hipEventRecord(d->ev[3], s));
-    HIPCHK(launch_sort(d->cand, d->keys, d->gscratch, d->cand_count, d->item_off, d->plan.nms_start[kMaxOct] * 4,
-                       d->cap, nframes, points, d->max_pts, counts, d->offsets, d->order, d->status, s, d->sw,
-                       d->keep));
+    HIPCHK(launch_sort(d->cands, d->plan, nframes, slots, d->schedule, s, d->sw, d->keep));
     if (prof) HIPCHK(hipEventRecord(d->ev[4], s));
     if (pf == kPrefDescribe) HIPCHK(prefetch_next(d, next, s));
     if (d->desc_ev) HIPCHK(hipEventRecord(d->desc_ev, s));
     if (desc)
-        HIPCHK(launch_describe(d->ii, d->P, points, d->max_pts, counts, d->offsets, d->order, d->work, nframes, desc,
-                               d->status + 64, s, pf == kPrefDescribe && !d->plan.iiw, d->cus, d->sw, how));
+        HIPCHK(launch_describe(d->ii, d->P, slots, d->schedule, nframes, desc, s, pf == kPrefDescribe && !d->plan.iiw,
+                               d->cus, d->sw, how));
     if (prof) HIPCHK(hipEventRecord(d->ev[5], s));
     d->last = b;
     return SURFHIP_OK;
@@ -1006,10 +989,10 @@ int surfhip_detect(surfhip_detector* d, const uint8_t* image, int pitch, surfhip
 int surfhip_detector_candidates(surfhip_detector* d, int* h_counts, int nframes)
 {
     if (!d || !h_counts || nframes < 1 || nframes > d->max_batch) return SURFHIP_ERR_INVALID;
-    HIPCHK(hipMemcpyAsync(h_counts, d->cand_count, sizeof(int) * nframes, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipMemcpyAsync(h_counts, d->cands.cand_count, sizeof(int) * nframes, hipMemcpyDeviceToHost, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
     int st = 0;
-    HIPCHK(hipMemcpy(&st, d->status, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&st, d->cands.status, sizeof(int), hipMemcpyDeviceToHost));
     return st ? SURFHIP_ERR_CAPACITY : SURFHIP_OK;
 }
 
@@ -1017,7 +1000,7 @@ int surfhip_detector_status(surfhip_detector* d, int* truncated)
 {
     if (!d || !truncated) return SURFHIP_ERR_INVALID;
     int st = 0;
-    HIPCHK(hipMemcpyAsync(&st, d->status, sizeof(int), hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipMemcpyAsync(&st, d->cands.status, sizeof(int), hipMemcpyDeviceToHost, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
     *truncated = st & 1;
     return SURFHIP_OK;
@@ -1043,7 +1026,7 @@ int surfhip_detector_get_keep(surfhip_detector* d, int* mode, int* n)
 int surfhip_detector_capacity(surfhip_detector* d, int* cand_cap)
 {
     if (!d || !cand_cap) return SURFHIP_ERR_INVALID;
-    *cand_cap = d->cap;
+    *cand_cap = d->cands.cap;
     return SURFHIP_OK;
 }
 
@@ -1146,14 +1129,13 @@ int surfhip_detector_switches(surfhip_detector* d, char* buf, int len)
 
 size_t surfhip_slab_bytes(int nframes, int total, int nfeatures)
 {
-    return 16 + (((size_t)nframes * 4 + 15) & ~(size_t)15) +
-           (size_t)total * (sizeof(surfhip_point) + sizeof(float) * (size_t)nfeatures);
+    return slab_head_bytes(nframes) + (size_t)total * (sizeof(surfhip_point) + sizeof(float) * (size_t)nfeatures);
 }
 
 int surfhip_batch_total(surfhip_detector* d, int nframes, int* total)
 {
     if (!d || !total || nframes < 1 || nframes > d->max_batch) return SURFHIP_ERR_INVALID;
-    HIPCHK(hipMemcpyAsync(total, d->offsets + nframes, sizeof(int), hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipMemcpyAsync(total, d->schedule.offsets + nframes, sizeof(int), hipMemcpyDeviceToHost, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
     return SURFHIP_OK;
 }
@@ -1163,8 +1145,8 @@ int surfhip_pack_slab_cap(surfhip_detector* d, const surfhip_point* pts, const f
 {
     if (!d || !pts || !counts || !slab || nframes < 1 || nframes > d->max_batch) return SURFHIP_ERR_INVALID;
     if (cap_bytes < surfhip_slab_bytes(nframes, 0, 0)) return SURFHIP_ERR_INVALID;
-    HIPCHK(launch_pack(pts, desc, counts, d->offsets, nframes, d->max_pts, d->param.nfeatures, d->status, cap_bytes,
-                       (uint8_t*)slab, d->stream));
+    HIPCHK(launch_pack(pts, desc, counts, d->schedule, nframes, d->max_pts, d->param.nfeatures, d->cands.status,
+                       cap_bytes, (uint8_t*)slab, d->stream));
     return SURFHIP_OK;
 }
 
@@ -1293,7 +1275,7 @@ static int ingest_alloc(surfhip_ingest* g)
     const int nf = d->param.nfeatures, B = d->max_batch;
     g->pitch = (d->srcW + 127) & ~127;
     g->frame_bytes = (size_t)g->pitch * d->srcH;
-    g->hdr_bytes = 16 + ((4 * B + 15) & ~15);
+    g->hdr_bytes = (int)slab_head_bytes(B);
     g->dslab_cap = surfhip_slab_bytes(B, B * d->max_pts, nf);
     HIPCHK(hipStreamCreateWithFlags(&g->copy, hipStreamNonBlocking));
     HIPCHK(hipStreamCreateWithFlags(&g->out, hipStreamNonBlocking));
@@ -1373,8 +1355,7 @@ int surfhip_ingest_submit(surfhip_ingest* g, int nframes)
     if (rc != SURFHIP_OK) return rc;
     rc = surfhip_pack_slab(d, g->d_pts, g->d_desc, g->d_counts, nframes, g->d_slab[s]);
     if (rc != SURFHIP_OK) return rc;
-    HIPCHK(hipMemcpyAsync(g->h_hdr[s], g->d_slab[s], 16 + ((4 * nframes + 15) & ~15), hipMemcpyDeviceToHost,
-                          d->stream));
+    HIPCHK(hipMemcpyAsync(g->h_hdr[s], g->d_slab[s], slab_head_bytes(nframes), hipMemcpyDeviceToHost, d->stream));
     HIPCHK(hipEventRecord(g->ev_done[s], d->stream));
     ++g->submitted;
     return SURFHIP_OK;

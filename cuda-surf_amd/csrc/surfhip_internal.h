@@ -194,11 +194,37 @@ hipError_t launch_rowseg(const FrameBatch& b, const FrameParams& P, const Launch
                          hipStream_t s);
 // NMS scan items: one wave's 64 block columns x kScanRows / 4 block rows;
 // each item owns kItemCap survivor slots (no atomics in the scan).
-// (also zeroes cand_count[0, nframes) and *status, the per-batch counters)
-hipError_t launch_nms(const int32_t* ii, const float* resp, int nframes, const FrameParams& P,
-                      const OctaveParams* d_oct, const LaunchPlan& plan, uint32_t* scan_key, uint32_t* scan_src,
-                      float* scan_cube, int* item_count, int* item_off, surfhip_point* cand, uint32_t* keys,
-                      int* cand_count, int cap, int* status, hipStream_t s, const Switches& sw, bool stash_trace);
+inline int scan_items(const LaunchPlan& plan) { return plan.nms_start[kMaxOct] * 4; }   // per frame
+// What the NMS stage produces and the sort consumes, per frame of n = scan_items(plan)
+struct Candidates {
+    uint32_t *scan_key, *scan_src;  // NMS survivors awaiting interpolation: n x kItemCap
+    float* scan_cube;               // the survivors' fit inputs: n x kCubeCap x kCubeF
+    int* item_count;                // survivors per scan item
+    int* item_off;                  // their exclusive prefix (+ total), then the scan's per-chunk totals
+    surfhip_point* cand;            // cap per frame, in scan order
+    uint32_t* keys;                 // their canonical keys; kNoKey: rejected by the fit
+    uint64_t* gscratch;             // cap > kSortCap: k_sort's sort space
+    int* cand_count;                // accepted candidates per frame
+    int cap;
+    int* status;                    // [0] bit 0: a frame was cut at cap; from [64]: DescribeSchedule::queue
+};
+// The describe schedule: written by launch_sort or launch_plant, read by launch_describe and launch_pack
+struct DescribeSchedule {
+    int* offsets;                   // exclusive prefix of the frames' counts (+ total)
+    int* order;                     // per frame: keypoint slots in describe order
+    float4* work;                   // the schedule flattened: max_pts x kWorkF4 float4 per frame (k_worklist)
+    int* queue;                     // kDescQueueBytes: the describe kernels' per-XCD work counters, 256 B apart
+};
+// The caller's output: frame f's points from pts[f * max_pts], counts[f] of them
+struct PointSlots {
+    surfhip_point* pts;
+    int max_pts;
+    int* counts;
+};
+// Scan, prefix and fit of a.b.n frames' planes a.resp into c (a.ii: the laplace sign's integral)
+// (also zeroes c.cand_count[0, a.b.n) and *c.status, the per-batch counters)
+hipError_t launch_nms(const HessianArgs& a, const Candidates& c, hipStream_t s, const Switches& sw,
+                      bool stash_trace);
 // The per-frame keypoint budget (surfhip_detector_set_keep): at most n (1 .. max_pts) points per frame, the
 // first n in canonical order or the n strongest.  valid: max_batch ints of device scratch, each frame's valid
 // candidates before k_keep_strongest's selection (SURFHIP_KEEP_STRONGEST only).
@@ -207,11 +233,10 @@ struct KeepRule {
     int n = 0;
     int* valid = nullptr;
 };
+// c's candidates of nframes (launch_nms's, of the same plan) in canonical order into out, their schedule into sch
 // (SURFHIP_KEEP_STRONGEST writes kNoKey over the keys of the candidates it drops)
-hipError_t launch_sort(const surfhip_point* cand, uint32_t* keys, uint64_t* gscratch,
-                       const int* cand_count, const int* soff, int items_per_frame, int cap, int nframes,
-                       surfhip_point* out, int max_pts, int* out_count, int* offsets, int* order, int* status,
-                       hipStream_t s, const Switches& sw, const KeepRule& keep);
+hipError_t launch_sort(const Candidates& c, const LaunchPlan& plan, int nframes, const PointSlots& out,
+                       const DescribeSchedule& sch, hipStream_t s, const Switches& sw, const KeepRule& keep);
 hipError_t set_max_lds(const void* fn, int bytes);
 // The describe kernel of a batch of nframes and where its laplace sign is
 // taken, chosen once per call (surfhip_detect_batch_next).  kDescU2: upright
@@ -227,22 +252,19 @@ struct DescribeChoice {
     bool trace;
 };
 DescribeChoice choose_describe(const Switches& sw, const FrameParams& P, int nframes);
-// queue: kDescQueueBytes of device scratch (the per-XCD work counters of
-// k_describe_ur, 8 x kDescQ of them 256 B apart, zeroed by the launch)
+// sch: pts' schedule (sch.queue is zeroed by the launch; sch.work is k_describe_u2's)
 // beside: another stream's kernels (the next batch's integral, not a mere
 // row-sum pass) run beside it, so the persistent grid leaves each CU a workgroup slot
-// work: max_batch * max_pts * kWorkF4 float4 of scratch (k_describe_u2's flattened schedule)
 // cus: compute units of the detector's device (sizes the persistent grid)
 // how: the batch's choose_describe(); its trace was the same call's stash_trace of launch_nms
-hipError_t launch_describe(const int32_t* ii, const FrameParams& P, surfhip_point* pts, int max_pts,
-                           const int* counts, const int* offsets, const int* order, float4* work, int nframes,
-                           float* desc, int* queue, hipStream_t s, bool beside, int cus, const Switches& sw,
-                           DescribeChoice how);
+hipError_t launch_describe(const int32_t* ii, const FrameParams& P, const PointSlots& pts,
+                           const DescribeSchedule& sch, int nframes, float* desc, hipStream_t s, bool beside,
+                           int cus, const Switches& sw, DescribeChoice how);
 // The describe schedule of caller-given points (surfhip_run_describe), in
-// place of launch_sort's: clamped[f] = counts[f] cut to [0, max_pts] (the
-// caller's counts stay as they are), their prefix in offsets (k_offsets) and
-// the identity order of each frame's first clamped[f] slots.
-hipError_t launch_plant(const int* counts, int nframes, int max_pts, int* clamped, int* offsets, int* order,
+// place of launch_sort's: pts.counts[f] = counts[f] cut to [0, max_pts] (the
+// caller's counts stay as they are), their prefix in sch.offsets (k_offsets)
+// and the identity order of each frame's first pts.counts[f] slots.
+hipError_t launch_plant(const int* counts, int nframes, const PointSlots& pts, const DescribeSchedule& sch,
                         hipStream_t s);
 // Doubled-image input (surfhip_double.hip): frames (W x H) -> D ((2W-2) x
 // (2H-2) u8, row pitch dpitch, a multiple of 4).
@@ -267,7 +289,10 @@ constexpr int kHomogCap = 3072;
 hipError_t launch_homography_batch(const surfhip_point* pts, const int* counts, int slots, int npairs, float max_amb,
                                    float thresh, int nhyp, uint32_t seed, surfhip_homography* out, uint8_t* inlier,
                                    hipStream_t s);
-hipError_t launch_pack(const surfhip_point* pts, const float* desc, const int* counts, const int* offsets,
+// bytes ahead of a result slab's points: int32 header[4], then the frames' counts padded to 16 B
+inline size_t slab_head_bytes(int nframes) { return 16 + (((size_t)nframes * 4 + 15) & ~(size_t)15); }
+// (sch.offsets: the prefix of counts, as the batch's launch_sort left it)
+hipError_t launch_pack(const surfhip_point* pts, const float* desc, const int* counts, const DescribeSchedule& sch,
                        int nframes, int max_pts, int nfeat, const int* status, size_t cap_bytes, uint8_t* slab,
                        hipStream_t s);
 

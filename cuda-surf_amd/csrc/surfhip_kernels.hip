@@ -690,8 +690,8 @@ __global__ __launch_bounds__(256) void k_worklist(const surfhip_point* __restric
     // left it to the describe, nms_fit_point):
     //   {dx, dy, spacing, f}  {ix, iy, step | hs << 10 | iradius << 22, f * max_pts + kp}
     //   {laplace, ori, 1 / spacing, 0}
-    // (10 / 12 / 10 bits: choose_describe takes this path only when the
-    // largest window of the detector's octaves fits, worklist_fits)
+    // (10 / 12 / 9 bits, iradius below the int's sign: choose_describe takes this path
+    // only when the largest window of the detector's octaves fits, worklist_fits)
     const int f = blockIdx.y, n = counts[f], o = offsets[f];
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
         const int idx = f * max_pts + order[(size_t)f * max_pts + i];
@@ -716,7 +716,10 @@ __global__ __launch_bounds__(256) void k_worklist(const surfhip_point* __restric
 // divisor (surfd.cu:1001-1022) at the top octave with s + off <= max_scale -
 // 1 + 1.5 (the fit's limits); describe uses 1.65 x (3.3 x doubled) of it
 // (surfd.cu:1581-1592); step = rn(S / 2) < 2^10, hs = rz(S) < 2^12, iradius
-// = rn(spacing (wsz + 1) / 2 / step) < 2^10.
+// = rn(spacing (wsz + 1) / 2 / step) < 2^9: it sits in bits 22-31 of a signed
+// int that k_describe_u2 decodes with an arithmetic shift.  The iradius bound
+// decides nothing: the path needs wsz 4, hence mag 3 and iradius = 7.5 S /
+// step + 1 with step = max(floor(S / 2 + 0.5), 1), below 24 for every S.
 static bool worklist_fits(const FrameParams& P)
 {
     const float oct = (float)(1 << (P.noct - 1));
@@ -724,7 +727,7 @@ static bool worklist_fits(const FrameParams& P)
     const float S = (P.doubled ? 3.3f : 1.65f) * 1.2f * ns * P.divisor;
     const float step = std::max(std::floor(S * 0.5f + 0.5f), 1.f);
     const float iradius = S * (float)P.mag * (float)(P.wsz + 1) * 0.5f / step + 1.f;
-    return S * 0.5f + 1.f < 1024.f && S + 1.f < 4096.f && iradius < 1024.f;
+    return S * 0.5f + 1.f < 1024.f && S + 1.f < 4096.f && iradius < 512.f;
 }
 
 DescribeChoice choose_describe(const Switches& sw, const FrameParams& P, int nframes)
@@ -748,9 +751,8 @@ DescribeChoice choose_describe(const Switches& sw, const FrameParams& P, int nfr
     return {P.wsz == 4 && !sw.rot_atomic ? kDescRot : kDescRotAtomic, false};
 }
 
-hipError_t launch_describe(const int32_t* ii, const FrameParams& P, surfhip_point* pts, int max_pts,
-                           const int* counts, const int* offsets, const int* order, float4* work, int nframes,
-                           float* desc, int* queue, hipStream_t s, bool beside, int cus, const Switches& sw,
+hipError_t launch_describe(const int32_t* ii, const FrameParams& P, const PointSlots& p, const DescribeSchedule& sch,
+                           int nframes, float* desc, hipStream_t s, bool beside, int cus, const Switches& sw,
                            DescribeChoice how)
 {
     if (P.nfeat > 512) return hipErrorInvalidValue;
@@ -759,41 +761,29 @@ hipError_t launch_describe(const int32_t* ii, const FrameParams& P, surfhip_poin
     // (SURFHIP_DESC_BESIDE workgroups per CU, default 3) a slot stays free
     if (cus <= 0) cus = 256;
     const int grid = (beside && sw.desc_beside > 0) ? ((sw.desc_beside * cus + 7) & ~7) : 2048;
-    hipError_t e = hipMemsetAsync(queue, 0, kDescQueueBytes, s);
+    hipError_t e = hipMemsetAsync(sch.queue, 0, kDescQueueBytes, s);
     if (e != hipSuccess) return e;
+    auto counted = [&](auto* k) {       // k_describe reads the counts, the others only their prefix
+        k<<<grid, 256, 0, s>>>(ii, P, p.pts, p.max_pts, p.counts, sch.offsets, sch.order, nframes, desc, sch.queue);
+    };
+    auto plain = [&](auto* k) {
+        k<<<grid, 256, 0, s>>>(ii, P, p.pts, p.max_pts, sch.offsets, sch.order, nframes, desc, sch.queue);
+    };
     switch (how.kernel) {
         case kDescU2: {         // the LDS-DMA ring
-            k_worklist<<<dim3(std::min(8, (max_pts + 255) / 256), nframes), 256, 0, s>>>(pts, max_pts, counts, offsets,
-                                                                                          order, work, P);
+            k_worklist<<<dim3(std::min(8, (p.max_pts + 255) / 256), nframes), 256, 0, s>>>(
+                p.pts, p.max_pts, p.counts, sch.offsets, sch.order, sch.work, P);
             // (diagnostic: SURFHIP_U2_LDSPAD bytes of unused dynamic LDS per workgroup)
-            const int pad = sw.u2_ldspad, tr = how.trace ? 1 : 0;
-            if (P.extend)
-                k_describe_u2<true><<<grid, 256, pad, s>>>(ii, P, work, max_pts, offsets, nframes, desc, queue, pts, tr);
-            else k_describe_u2<false><<<grid, 256, pad, s>>>(ii, P, work, max_pts, offsets, nframes, desc, queue, pts, tr);
+            auto* k = P.extend ? &k_describe_u2<true> : &k_describe_u2<false>;
+            k<<<grid, 256, sw.u2_ldspad, s>>>(ii, P, sch.work, p.max_pts, sch.offsets, nframes, desc, sch.queue, p.pts,
+                                              how.trace ? 1 : 0);
             break;
         }
-        case kDescUr:           // round 3's upright kernel
-            if (P.extend)
-                k_describe_ur<true><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, offsets, order, nframes, desc, queue);
-            else k_describe_ur<false><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, offsets, order, nframes, desc, queue);
-            break;
-        case kDescWide:
-            if (P.upright)
-                k_describe<true, 512><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, counts, offsets, order, nframes, desc, queue);
-            else
-                k_describe<false, 512><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, counts, offsets, order, nframes, desc, queue);
-            break;
-        case kDescUpright:
-            k_describe<true, 128><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, counts, offsets, order, nframes, desc, queue);
-            break;
-        case kDescRot:
-            if (P.osz == 8)
-                k_describe_rot<8><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, offsets, order, nframes, desc, queue);
-            else k_describe_rot<4><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, offsets, order, nframes, desc, queue);
-            break;
-        case kDescRotAtomic:
-            k_describe<false, 128><<<grid, 256, 0, s>>>(ii, P, pts, max_pts, counts, offsets, order, nframes, desc, queue);
-            break;
+        case kDescUr: plain(P.extend ? &k_describe_ur<true> : &k_describe_ur<false>); break;    // round 3's kernel
+        case kDescWide: counted(P.upright ? &k_describe<true, 512> : &k_describe<false, 512>); break;
+        case kDescUpright: counted(&k_describe<true, 128>); break;
+        case kDescRot: plain(P.osz == 8 ? &k_describe_rot<8> : &k_describe_rot<4>); break;
+        case kDescRotAtomic: counted(&k_describe<false, 128>); break;
     }
     return hipGetLastError();
 }
@@ -844,11 +834,11 @@ __global__ __launch_bounds__(256) void k_pack(const surfhip_point* __restrict__ 
     }
 }
 
-hipError_t launch_pack(const surfhip_point* pts, const float* desc, const int* counts, const int* offsets,
+hipError_t launch_pack(const surfhip_point* pts, const float* desc, const int* counts, const DescribeSchedule& sch,
                        int nframes, int max_pts, int nfeat, const int* status, size_t cap_bytes, uint8_t* slab,
                        hipStream_t s)
 {
-    k_pack<<<dim3(16, nframes), 256, 0, s>>>(pts, desc, counts, offsets, nframes, max_pts, nfeat, status,
+    k_pack<<<dim3(16, nframes), 256, 0, s>>>(pts, desc, counts, sch.offsets, nframes, max_pts, nfeat, status,
                                              cap_bytes, slab);
     return hipGetLastError();
 }
@@ -866,11 +856,12 @@ __global__ __launch_bounds__(THREADS) void k_plant(const int* __restrict__ count
         order[(size_t)f * max_pts + i] = i;
 }
 
-hipError_t launch_plant(const int* counts, int nframes, int max_pts, int* clamped, int* offsets, int* order,
+hipError_t launch_plant(const int* counts, int nframes, const PointSlots& pts, const DescribeSchedule& sch,
                         hipStream_t s)
 {
-    k_plant<256><<<dim3(std::min(8, (max_pts + 255) / 256), nframes), 256, 0, s>>>(counts, max_pts, clamped, order);
-    k_offsets<<<1, 1024, 0, s>>>(clamped, nframes, offsets);
+    k_plant<256><<<dim3(std::min(8, (pts.max_pts + 255) / 256), nframes), 256, 0, s>>>(counts, pts.max_pts, pts.counts,
+                                                                                       sch.order);
+    k_offsets<<<1, 1024, 0, s>>>(pts.counts, nframes, sch.offsets);
     return hipGetLastError();
 }
 

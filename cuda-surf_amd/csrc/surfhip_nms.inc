@@ -693,30 +693,28 @@ __global__ __launch_bounds__(256) void k_nms_fit(const int32_t* __restrict__ ii,
     }
 }
 
-hipError_t launch_nms(const int32_t* ii, const float* resp, int nframes, const FrameParams& P,
-                      const OctaveParams* d_oct, const LaunchPlan& plan, uint32_t* scan_key, uint32_t* scan_src,
-                      float* scan_cube, int* item_count, int* item_off, surfhip_point* cand, uint32_t* keys,
-                      int* cand_count, int cap, int* status, hipStream_t s, const Switches& sw, bool stash_trace)
+hipError_t launch_nms(const HessianArgs& a, const Candidates& c, hipStream_t s, const Switches& sw, bool stash_trace)
 {
-    const int per = plan.nms_start[kMaxOct];
+    const LaunchPlan& plan = *a.plan;
+    const int nframes = a.b.n, per = plan.nms_start[kMaxOct];
     if (per == 0) {
         // (no NMS level: nothing to scan; the counters the sort reads are 0)
-        hipError_t e = hipMemsetAsync(cand_count, 0, sizeof(int) * (size_t)nframes, s);
-        if (e == hipSuccess) e = hipMemsetAsync(status, 0, sizeof(int), s);
+        hipError_t e = hipMemsetAsync(c.cand_count, 0, sizeof(int) * (size_t)nframes, s);
+        if (e == hipSuccess) e = hipMemsetAsync(c.status, 0, sizeof(int), s);
         return e;
     }
     // the scan's fit records for every batch size (round 5: one 1080p frame's
     // NMS 0.038 -> 0.034 ms with them; round 2's cross-lane variant had made
     // single frames slower); SURFHIP_FIT_CUBE=0: the fit reads the planes (A/B)
     const bool cube = sw.fit_cube;
-    if (!cube) scan_cube = nullptr;
+    float* scan_cube = cube ? c.scan_cube : nullptr;
     auto* scan = cube ? &k_nms_scan<true> : &k_nms_scan<false>;
-    scan<<<dim3(frame_grid(nframes) * per), 256, 0, s>>>(resp, P, d_oct, plan, scan_key, scan_src, scan_cube,
-                                                                item_count, nframes, cand_count, status);
-    const int nitems = nframes * per * 4;
-    launch_excl_scan(item_count, nitems, item_off, item_off + nitems + 1, s);
+    scan<<<dim3(frame_grid(nframes) * per), 256, 0, s>>>(a.resp, *a.P, a.d_oct, plan, c.scan_key, c.scan_src, scan_cube,
+                                                                c.item_count, nframes, c.cand_count, c.status);
+    const int items = scan_items(plan), nitems = nframes * items;
+    launch_excl_scan(c.item_count, nitems, c.item_off, c.item_off + nitems + 1, s);
     // 5 waves per SIMD fit (90 VGPRs) = 1,280 workgroups of 4 waves; SURFHIP_FIT_GRID overrides (A/B)
-    k_nms_fit<<<sw.fit_grid, 256, 0, s>>>(ii, resp, P, d_oct, scan_key, scan_src, scan_cube, item_off, nitems, per * 4,
-                                          cand, keys, cand_count, cap, stash_trace ? 1 : 0);
+    k_nms_fit<<<sw.fit_grid, 256, 0, s>>>(a.ii, a.resp, *a.P, a.d_oct, c.scan_key, c.scan_src, scan_cube, c.item_off,
+                                          nitems, items, c.cand, c.keys, c.cand_count, c.cap, stash_trace ? 1 : 0);
     return hipGetLastError();
 }

@@ -337,11 +337,10 @@ __global__ __launch_bounds__(1024) void k_offsets(const int* __restrict__ counts
         if (b + i < nframes) { offsets[b + i] = run; run += counts[b + i]; }
 }
 
-hipError_t launch_sort(const surfhip_point* cand, uint32_t* keys, uint64_t* gscratch,
-                       const int* cand_count, const int* soff, int items_per_frame, int cap, int nframes,
-                       surfhip_point* out, int max_pts, int* out_count, int* offsets, int* order, int* status,
-                       hipStream_t s, const Switches& sw, const KeepRule& keep)
+hipError_t launch_sort(const Candidates& c, const LaunchPlan& plan, int nframes, const PointSlots& out,
+                       const DescribeSchedule& sch, hipStream_t s, const Switches& sw, const KeepRule& keep)
 {
+    const int items = scan_items(plan), cap = c.cap;
     // SURFHIP_KEEP_STRONGEST: the losers' keys become kNoKey ahead of the sort
     // (SURFHIP_KEEP_FIRST is the sort kernels' own cut at keep.n)
     const int* pre_valid = nullptr;
@@ -349,7 +348,7 @@ hipError_t launch_sort(const surfhip_point* cand, uint32_t* keys, uint64_t* gscr
         const int slots = std::min(cap, kSortCap);
         hipError_t e = set_max_lds(reinterpret_cast<const void*>(&k_keep_strongest), (int)(kSortCap * sizeof(uint64_t)));
         if (e != hipSuccess) return e;
-        k_keep_strongest<<<nframes, 1024, slots * sizeof(uint64_t), s>>>(cand, keys, soff, items_per_frame, cap, slots,
+        k_keep_strongest<<<nframes, 1024, slots * sizeof(uint64_t), s>>>(c.cand, c.keys, c.item_off, items, cap, slots,
                                                                          keep.n, keep.valid);
         pre_valid = keep.valid;
     }
@@ -358,15 +357,15 @@ hipError_t launch_sort(const surfhip_point* cand, uint32_t* keys, uint64_t* gscr
         // candidates of a 1080p frame: 188), beyond that each takes several
         // groups of 16 with the keys it staged once
         const int per = std::min((cap + 256 / kRankT - 1) / (256 / kRankT), kRankMaxWgs);
-        k_sort_rank<<<nframes * per, 256, 0, s>>>(cand, keys, cand_count, soff, items_per_frame, cap, per, out,
-                                                  max_pts, out_count, order, status, keep.n, pre_valid);
+        k_sort_rank<<<nframes * per, 256, 0, s>>>(c.cand, c.keys, c.cand_count, c.item_off, items, cap, per, out.pts,
+                                                  out.max_pts, out.counts, sch.order, c.status, keep.n, pre_valid);
     } else {
         hipError_t e = set_max_lds(reinterpret_cast<const void*>(&k_sort), (int)(kSortCap * sizeof(uint64_t)));
         if (e != hipSuccess) return e;
-        k_sort<<<nframes, 1024, kSortCap * sizeof(uint64_t), s>>>(cand, keys, gscratch, cand_count, soff,
-                                                                  items_per_frame, cap, out, max_pts, out_count,
-                                                                  order, status, keep.n, pre_valid);
+        k_sort<<<nframes, 1024, kSortCap * sizeof(uint64_t), s>>>(c.cand, c.keys, c.gscratch, c.cand_count, c.item_off,
+                                                                  items, cap, out.pts, out.max_pts, out.counts,
+                                                                  sch.order, c.status, keep.n, pre_valid);
     }
-    k_offsets<<<1, 1024, 0, s>>>(out_count, nframes, offsets);
+    k_offsets<<<1, 1024, 0, s>>>(out.counts, nframes, sch.offsets);
     return hipGetLastError();
 }
