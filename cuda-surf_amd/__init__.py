@@ -134,6 +134,8 @@ _sigs = {
     "surfhip_match_scratch": (_sz, [_i, _i, _i]),
     "surfhip_match": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "surfhip_match_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "surfhip_match_batch_cross_scratch": (_sz, [_i, _i, _i]),
+    "surfhip_match_batch_cross": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "surfhip_homography_batch": (_i, [_vp, _vp, _i, _i, C.c_float, C.c_float, _i, C.c_uint32, _vp, _vp, _vp]),
     "surfhip_homography_lds_capacity": (_i, []),
     "surfhip_ingest_create": (_i, [C.POINTER(_vp), _vp, _i]),
@@ -624,6 +626,23 @@ def match_batch(pts1_ptr: int, desc1_ptr: int, counts1_ptr: int, slots1: int, pt
     npairs = nframes - 1."""
     check(_lib.surfhip_match_batch(pts1_ptr, desc1_ptr, counts1_ptr, slots1, pts2_ptr, desc2_ptr, counts2_ptr,
                                    slots2, npairs, nfeatures, flags, stream), "surfhip_match_batch")
+
+
+def match_batch_cross_scratch_bytes(npairs: int, slots1: int, slots2: int) -> int:
+    return int(_lib.surfhip_match_batch_cross_scratch(npairs, slots1, slots2))
+
+
+def match_batch_cross(pts1_ptr: int, desc1_ptr: int, counts1_ptr: int, slots1: int, pts2_ptr: int, desc2_ptr: int,
+                      counts2_ptr: int, slots2: int, npairs: int, nfeatures: int, scratch_ptr: int, flags: int = 0,
+                      stream=None) -> None:
+    """surfhip_match_batch_cross: match_batch with the mutual-best test (a
+    match p1 -> p2 stays only when p1 is also the best set-1 point of p2; the
+    others get match = -1, match_x = match_y = 0 and keep score and
+    ambiguity).  scratch_ptr: match_batch_cross_scratch_bytes(...) of device
+    memory in any state; the call clears it on `stream`."""
+    check(_lib.surfhip_match_batch_cross(pts1_ptr, desc1_ptr, counts1_ptr, slots1, pts2_ptr, desc2_ptr, counts2_ptr,
+                                         slots2, npairs, nfeatures, flags, scratch_ptr, stream),
+          "surfhip_match_batch_cross")
 
 
 # ------------------------------------------------------------ homography

@@ -282,6 +282,13 @@ hipError_t launch_match(surfhip_point* pts1, const surfhip_point* pts2, const fl
 hipError_t launch_match_batch(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
                               const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
                               int npairs, int nf, int flags, hipStream_t s);
+// The same with the mutual-best filter: a match (p1 -> p2) stays only when p1
+// is the best set-1 point of p2.  scratch: match_batch_cross_scratch_bytes()
+// of device memory in any state (one 64-bit word per set-2 slot, cleared on s).
+size_t match_batch_cross_scratch_bytes(int npairs, int slots2);
+hipError_t launch_match_batch_cross(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
+                                    const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
+                                    int npairs, int nf, int flags, void* scratch, hipStream_t s);
 // Batched RANSAC homographies (surfhip_homography.hip): one workgroup per
 // pair on the match fields of its set-1 points; kHomogCap candidates per
 // pair stay in LDS, more are re-read from the point array.

@@ -46,6 +46,16 @@
 //     are read on the device: no scratch, no host sync, one launch.
 //   * k_match_batch_any: other descriptor lengths, both operands reloaded
 //     from memory at every k-step.
+//
+// Mutual-best matching (surfhip_match_batch_cross) keeps a forward match
+// (p1 -> p2) only when p1 is also the best set-1 point of p2.  fmaf(a, b, c)
+// == fmaf(b, a, c), so the back direction's scores are the tile D[p2][p1]
+// the forward kernels already hold: their CROSS instantiations reduce each
+// tile's columns over the lanes (the maximum positive score, the lowest p1
+// on a tie), combine the block's waves in LDS and send one 64-bit integer
+// atomic max per (block, p2) to a caller-provided word per set-2 slot -- no
+// second score pass, and an integer maximum does not depend on arrival
+// order.  k_match_cross_filter then clears the matches that are not mutual.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -228,9 +238,13 @@ __device__ __forceinline__ int clamp_count(int c, int slots) { return c < 0 ? 0 
 // One 32 x 32 score tile D[p2][p1] into the lane's four row states: register
 // 4 q + r holds tile position 8 q + 4 h + r, i.e. thread row 2 q + h, r
 // ascending.  lap2: the laplace of tile position (lane & 31), LAP only.
-template <bool LAP>
+// CROSS: ks[4 q + r] also gets the score's bits where the pair (p1, p2) counts
+// for the back direction (p2 offered, p1 live, score > 0 -- never a NaN), 0
+// elsewhere; positive floats order like their bits.
+template <bool LAP, bool CROSS = false>
 __device__ __forceinline__ void scan_tile(const f32x16& acc, int t, int h, int nscan, int lap1, int lap2,
-                                          float (&mx)[4], float (&sc)[4], int (&ix)[4])
+                                          float (&mx)[4], float (&sc)[4], int (&ix)[4], bool live1 = false,
+                                          uint32_t* ks = nullptr)
 {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -244,8 +258,67 @@ __device__ __forceinline__ void scan_tile(const f32x16& acc, int t, int h, int n
                 ok = ok && l2 == lap1;
             }
             if (ok) scan_update(acc[4 * q + r], p2, mx[q], sc[q], ix[q]);
+            if constexpr (CROSS) {
+                const float s = acc[4 * q + r];
+                ks[4 * q + r] = (ok && live1 && s > 0.0f) ? __float_as_uint(s) : 0u;
+            }
         }
     }
+}
+
+// ---- mutual-best matching: the back direction's column maxima ------------
+// A key is (score bits << 32) | ~p1: the integer maximum is the largest
+// positive score and, among equal scores, the lowest p1; 0 means "none".
+typedef unsigned long long u64;
+
+// The value of lane (lane ^ X), X < 32: DPP inside a quad, the LDS crossbar
+// (ds_swizzle, bit mode: and 0x1f, or 0, xor X) beyond it.
+template <int X>
+__device__ __forceinline__ uint32_t lane_xor(uint32_t v)
+{
+    if constexpr (X == 1)
+        return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
+    else if constexpr (X == 2)
+        return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
+    else
+        return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, (X << 10) | 0x1F);
+}
+
+// One step of a transposing reduction over lane bit X: the lane keeps the
+// entries 2 k + (its bit X) of N and takes its partner's maxima for them, so
+// N entries become N / 2 that cover twice the lanes.
+template <int N, int X>
+__device__ __forceinline__ void cross_fold(uint32_t (&ks)[16], uint32_t (&ki)[16], bool up)
+{
+#pragma unroll
+    for (int k = 0; k < N / 2; ++k) {
+        const uint32_t keep_s = up ? ks[2 * k + 1] : ks[2 * k], keep_i = up ? ki[2 * k + 1] : ki[2 * k];
+        const uint32_t send_s = up ? ks[2 * k] : ks[2 * k + 1], send_i = up ? ki[2 * k] : ki[2 * k + 1];
+        const uint32_t rs = lane_xor<X>(send_s), ri = lane_xor<X>(send_i);
+        const bool take = (((u64)rs << 32) | ri) > (((u64)keep_s << 32) | keep_i);
+        ks[k] = take ? rs : keep_s;
+        ki[k] = take ? ri : keep_i;
+    }
+}
+
+// The 32 column maxima of a wave's 32 x 32 tile: ks as scan_tile<CROSS> left
+// it.  Returns, on the lanes with (lane & 31) < 16, the key of tile position
+// j (also returned) over the wave's 32 set-1 points: lane (h, c) ends with
+// register c of half h, position 8 (c >> 2) + 4 h + (c & 3).
+__device__ __forceinline__ u64 cross_reduce(uint32_t (&ks)[16], int p1, int h, int c, int& j)
+{
+    uint32_t ki[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) ki[i] = ~(uint32_t)p1;
+    cross_fold<16, 1>(ks, ki, c & 1);
+    cross_fold<8, 2>(ks, ki, c & 2);
+    cross_fold<4, 4>(ks, ki, c & 4);
+    cross_fold<2, 8>(ks, ki, c & 8);
+    const uint32_t rs = lane_xor<16>(ks[0]), ri = lane_xor<16>(ki[0]);
+    const u64 mine = ((u64)ks[0] << 32) | ki[0], other = ((u64)rs << 32) | ri;
+    j = 8 * ((c >> 2) & 3) + 4 * h + (c & 3);
+    const u64 key = other > mine ? other : mine;
+    return (key >> 32) ? key : 0;
 }
 
 // Lanes l and l ^ 32 hold rows (0, 2, 4, 6) and (1, 3, 5, 7) of point p1;
@@ -288,19 +361,24 @@ __device__ __forceinline__ void batch_finish(surfhip_point* pts1, const surfhip_
 // pts1 / pts2 may overlap (consecutive frames of one batch): no __restrict__
 // on them; only the five match fields of pts1 are written and only x, y,
 // laplace of pts2 are read.
-template <int NF, bool LAP>
+// CROSS (surfhip_match_batch_cross): the tile's column maxima, which the
+// forward scan throws away, also go to back[pair][p2] as keys: the four
+// waves' maxima meet in LDS (ds_max_u64), and one tile later wave 0 sends the
+// block's 32 keys with one 256-B atomic-max instruction.
+template <int NF, bool LAP, bool CROSS>
 __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pts1, const float* __restrict__ f1,
                                                                const int* __restrict__ counts1, int slots1,
                                                                const surfhip_point* pts2,
                                                                const float* __restrict__ f2,
                                                                const int* __restrict__ counts2, int slots2,
-                                                               int full_tail)
+                                                               int full_tail, u64* __restrict__ back)
 {
     constexpr int RS = NF + 4;                              // LDS row: NF / 2 even, NF / 2 odd elements, pad
     constexpr int C4 = NF / 4;                              // float4 per descriptor
     constexpr int NV = 32 * C4 / kBatchThreads;             // float4 per thread per tile
     static_assert(32 * C4 % kBatchThreads == 0, "tile staging");
     __shared__ __attribute__((aligned(16))) float tile[2][32 * RS];
+    __shared__ u64 colmax[CROSS ? 2 : 1][32];               // CROSS: the block's keys of tiles t and t + 1
 
     const int pair = blockIdx.y;
     const int n1 = clamp_count(counts1[pair], slots1);
@@ -313,6 +391,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pt
     pts2 += (size_t)pair * slots2;
     f1 += (size_t)pair * slots1 * NF;
     f2 += (size_t)pair * slots2 * NF;
+    if constexpr (CROSS) back += (size_t)pair * slots2;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int h = lane >> 5, c = lane & 31;
@@ -364,6 +443,20 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pt
         }
     };
 
+    // CROSS: tile u's keys leave colmax[u & 1], which is zero again for tile
+    // u + 2 (a key of 0 is "none": nothing to send, and a sent key has
+    // 32 u + lane < nscan)
+    auto send_keys = [&](int u) {
+        if (tid < 32) {
+            const u64 key = colmax[u & 1][tid];
+            colmax[u & 1][tid] = 0;
+            if (key) __hip_atomic_fetch_max(back + 32 * u + tid, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    };
+    if constexpr (CROSS) {
+        if (tid < 64) colmax[tid >> 5][tid & 31] = 0;
+    }
+
     if (ntile > 0) {
         load_tile(0);
         store_tile(0);
@@ -378,6 +471,9 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pt
         // of the MFMAs they are meant to run under
         load_tile(t + 1);
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (CROSS) {
+            if (wave == 0 && t > 0) send_keys(t - 1);       // ahead of the MFMAs, which cover the atomics' latency
+        }
         if (wlive) {
             const float4* ap = reinterpret_cast<const float4*>(&tile[cur][c * RS + h * (NF / 2)]);
             f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -389,26 +485,39 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pt
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b[4 * k + 2], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b[4 * k + 3], acc, 0, 0, 0);
             }
-            scan_tile<LAP>(acc, t, h, nscan, lap1, lap2, mx, sc, ix);
+            if constexpr (CROSS) {
+                uint32_t ks[16];
+                scan_tile<LAP, true>(acc, t, h, nscan, lap1, lap2, mx, sc, ix, p1 < n1, ks);
+                int j;
+                const u64 key = cross_reduce(ks, p1, h, c, j);
+                if (c < 16 && key)
+                    __hip_atomic_fetch_max(&colmax[cur][j], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            } else {
+                scan_tile<LAP>(acc, t, h, nscan, lap1, lap2, mx, sc, ix);
+            }
         }
         __builtin_amdgcn_sched_barrier(0);
         if (more) store_tile(cur ^ 1);
         lap2 = lapn;
         __syncthreads();
     }
+    if constexpr (CROSS) {
+        if (wave == 0 && ntile > 0) send_keys(ntile - 1);
+    }
     if (wlive) batch_finish(pts1, pts2, p1, n1, h, mx, sc, ix);
 }
 
 // Any descriptor length (a multiple of 4, <= 1024): both operands come from
 // memory at every k-step; no LDS, so a wave past n1 exits at once.
-template <bool LAP>
+// CROSS: every wave sends its own 32 keys per tile.
+template <bool LAP, bool CROSS>
 __global__ __launch_bounds__(kBatchThreads) void k_match_batch_any(surfhip_point* pts1,
                                                                    const float* __restrict__ f1,
                                                                    const int* __restrict__ counts1, int slots1,
                                                                    const surfhip_point* pts2,
                                                                    const float* __restrict__ f2,
                                                                    const int* __restrict__ counts2, int slots2,
-                                                                   int nf, int full_tail)
+                                                                   int nf, int full_tail, u64* __restrict__ back)
 {
     const int pair = blockIdx.y;
     const int n1 = clamp_count(counts1[pair], slots1);
@@ -422,6 +531,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch_any(surfhip_point
     pts2 += (size_t)pair * slots2;
     f1 += (size_t)pair * slots1 * nf;
     f2 += (size_t)pair * slots2 * nf;
+    if constexpr (CROSS) back += (size_t)pair * slots2;
     const int h = lane >> 5, c = lane & 31;
     const int p1 = base + c;
     const int q1 = p1 < n1 ? p1 : n1 - 1;
@@ -441,9 +551,36 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch_any(surfhip_point
         const int lap2 = LAP ? pts2[q2].laplace : 0;
         f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         for (int d = 0; d < nf; d += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(r2[d], r1[d], acc, 0, 0, 0);
-        scan_tile<LAP>(acc, t, h, nscan, lap1, lap2, mx, sc, ix);
+        if constexpr (CROSS) {
+            uint32_t ks[16];
+            scan_tile<LAP, true>(acc, t, h, nscan, lap1, lap2, mx, sc, ix, p1 < n1, ks);
+            int j;
+            const u64 key = cross_reduce(ks, p1, h, c, j);
+            if (c < 16 && key)                              // a key: 32 t + j < nscan
+                __hip_atomic_fetch_max(back + 32 * t + j, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else {
+            scan_tile<LAP>(acc, t, h, nscan, lap1, lap2, mx, sc, ix);
+        }
     }
     batch_finish(pts1, pts2, p1, n1, h, mx, sc, ix);
+}
+
+// The mutual-best filter, one thread per set-1 point below n1: a match whose
+// set-2 point has another back best (the key's low word is not ~p1) is
+// cleared; score and ambiguity stay the forward values.
+__global__ __launch_bounds__(256) void k_match_cross_filter(surfhip_point* pts1, const int* __restrict__ counts1,
+                                                            int slots1, int slots2, const u64* __restrict__ back)
+{
+    const int pair = blockIdx.y;
+    const int p1 = blockIdx.x * 256 + threadIdx.x;
+    if (p1 >= clamp_count(counts1[pair], slots1)) return;
+    surfhip_point& q = pts1[(size_t)pair * slots1 + p1];
+    const int m = q.match;
+    if (m < 0 || m >= slots2) return;                       // (the forward pass writes -1 or an index below n2)
+    if ((uint32_t)back[(size_t)pair * slots2 + m] == ~(uint32_t)p1) return;
+    q.match = -1;
+    q.match_x = 0.0f;
+    q.match_y = 0.0f;
 }
 
 }  // namespace
@@ -480,25 +617,29 @@ hipError_t launch_match(surfhip_point* pts1, const surfhip_point* pts2, const fl
     return hipGetLastError();
 }
 
-template <bool LAP>
+template <bool LAP, bool CROSS>
 static void launch_match_batch_lap(dim3 grid, surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
                                    const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
-                                   int nf, int full_tail, hipStream_t s)
+                                   int nf, int full_tail, u64* back, hipStream_t s)
 {
     if (nf == 64)
-        k_match_batch<64, LAP><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2,
-                                                              full_tail);
+        k_match_batch<64, LAP, CROSS><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2, counts2,
+                                                                     slots2, full_tail, back);
     else if (nf == 128)
-        k_match_batch<128, LAP><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2,
-                                                               full_tail);
+        k_match_batch<128, LAP, CROSS><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2, counts2,
+                                                                      slots2, full_tail, back);
     else
-        k_match_batch_any<LAP><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2,
-                                                              nf, full_tail);
+        k_match_batch_any<LAP, CROSS><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2, counts2,
+                                                                     slots2, nf, full_tail, back);
 }
 
-hipError_t launch_match_batch(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
-                              const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
-                              int npairs, int nf, int flags, hipStream_t s)
+// back == nullptr: the forward match alone.  Otherwise back[npairs][slots2]
+// keys, zero on entry, get the back direction's best and the filter pass
+// follows each launch (the kernel boundary makes the keys visible to it).
+template <bool CROSS>
+static hipError_t launch_match_batch_pass(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
+                                          const surfhip_point* pts2, const float* f2, const int* counts2,
+                                          int slots2, int npairs, int nf, int flags, u64* back, hipStream_t s)
 {
     const int full_tail = (flags & SURFHIP_MATCH_FULL_TAIL) ? 1 : 0;
     constexpr int kMaxGridY = 65535;                        // one launch up to this many pairs
@@ -509,16 +650,45 @@ hipError_t launch_match_batch(surfhip_point* pts1, const float* f1, const int* c
         const surfhip_point* b = pts2 + (size_t)p0 * slots2;
         const float* fa = f1 + (size_t)p0 * slots1 * nf;
         const float* fb = f2 + (size_t)p0 * slots2 * nf;
+        u64* bk = CROSS ? back + (size_t)p0 * slots2 : nullptr;
         if (flags & SURFHIP_MATCH_SAME_LAPLACE)
-            launch_match_batch_lap<true>(grid, a, fa, counts1 + p0, slots1, b, fb, counts2 + p0, slots2, nf,
-                                         full_tail, s);
+            launch_match_batch_lap<true, CROSS>(grid, a, fa, counts1 + p0, slots1, b, fb, counts2 + p0, slots2, nf,
+                                                full_tail, bk, s);
         else
-            launch_match_batch_lap<false>(grid, a, fa, counts1 + p0, slots1, b, fb, counts2 + p0, slots2, nf,
-                                          full_tail, s);
-        const hipError_t e = hipGetLastError();
+            launch_match_batch_lap<false, CROSS>(grid, a, fa, counts1 + p0, slots1, b, fb, counts2 + p0, slots2, nf,
+                                                 full_tail, bk, s);
+        hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
+        if (CROSS) {
+            k_match_cross_filter<<<dim3((slots1 + 255) / 256, np), 256, 0, s>>>(a, counts1 + p0, slots1, slots2, bk);
+            e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
     }
     return hipSuccess;
+}
+
+hipError_t launch_match_batch(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
+                              const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
+                              int npairs, int nf, int flags, hipStream_t s)
+{
+    return launch_match_batch_pass<false>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf, flags,
+                                          nullptr, s);
+}
+
+size_t match_batch_cross_scratch_bytes(int npairs, int slots2)
+{
+    return npairs > 0 && slots2 > 0 ? sizeof(u64) * (size_t)npairs * (size_t)slots2 : 0;
+}
+
+hipError_t launch_match_batch_cross(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
+                                    const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
+                                    int npairs, int nf, int flags, void* scratch, hipStream_t s)
+{
+    const hipError_t e = hipMemsetAsync(scratch, 0, match_batch_cross_scratch_bytes(npairs, slots2), s);
+    if (e != hipSuccess) return e;
+    return launch_match_batch_pass<true>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf, flags,
+                                         static_cast<u64*>(scratch), s);
 }
 
 }  // namespace surfhip

@@ -393,8 +393,8 @@ int surfhip_match(surfhip_point* d_pts1, const surfhip_point* d_pts2, const floa
  * d_counts + 1) and npairs = nframes - 1.  The buffers then overlap; this is
  * supported: only the five match fields of set-1 points are written and
  * only x, y and laplace of set-2 points are read.
- * flags: SURFHIP_MATCH_FULL_TAIL as above; SURFHIP_MATCH_SAME_LAPLACE (this
- * call only) offers a set-2 point to a set-1 point's top-2 scan only when
+ * flags: SURFHIP_MATCH_FULL_TAIL as above; SURFHIP_MATCH_SAME_LAPLACE (the
+ * batched calls only) offers a set-2 point to a set-1 point's top-2 scan only when
  * their `laplace` fields are equal (the classic SURF sign-of-Laplacian
  * pruning); a skipped point keeps its position in its 32-point tile.
  * nfeatures: a multiple of 4, 4 .. 1024.  SURFHIP_ERR_INVALID for
@@ -406,6 +406,41 @@ int surfhip_match(surfhip_point* d_pts1, const surfhip_point* d_pts2, const floa
 int surfhip_match_batch(surfhip_point* d_pts1, const float* d_desc1, const int* d_counts1, int slots1,
                         const surfhip_point* d_pts2, const float* d_desc2, const int* d_counts2, int slots2,
                         int npairs, int nfeatures, int flags, void* stream);
+
+/* Batched matching with the mutual-best test (OpenCV's crossCheck): the
+ * layouts, count clamping, flags, nfeatures rule and argument checks of
+ * surfhip_match_batch, plus a scratch buffer.  For pair i with clamped
+ * counts n1, n2, the scanned set-2 points [0, nscan) (nscan = n2 with
+ * SURFHIP_MATCH_FULL_TAIL, else 32 * (n2 / 32)) and S(p1, p2) the score:
+ *   forward  F(p1): the five fields surfhip_match_batch writes with the same
+ *            flags, bit for bit.
+ *   back     B(p2), p2 < nscan: the p1 in [0, n1) with the largest
+ *            S(p1, p2) > 0 among the points p2 is offered to (all of them, or
+ *            with SURFHIP_MATCH_SAME_LAPLACE those of equal `laplace`); the
+ *            lowest p1 on a tie, -1 when there is none.  A NaN score never
+ *            wins.  Every set-1 point below n1 takes part.
+ *   output   point p1 gets F(p1), except that a match I >= 0 with B(I) != p1
+ *            is cleared: match = -1, match_x = match_y = 0; its score and
+ *            ambiguity stay the forward values.  The kept matches of a pair
+ *            are injective (no two points share a partner), and
+ *            surfhip_homography_batch skips the cleared ones.
+ * Nothing else is written: not the other point fields, slots at or past n1,
+ * the descriptors or set 2 (of which only x, y, laplace are read), so the
+ * consecutive-frames layout (set 2 = set 1 advanced one frame) is supported
+ * as in surfhip_match_batch.  Every score is computed once: the forward
+ * kernel's score tiles also feed the back direction.  Results are the same
+ * bits from run to run and at every position of a batch.
+ * d_scratch: surfhip_match_batch_cross_scratch(npairs, slots1, slots2) bytes
+ * of device memory, 16-B aligned (8 * npairs * slots2: one word per set-2
+ * slot; 0 for non-positive arguments).  It may hold anything on entry; the
+ * call clears it on `stream`.  Asynchronous on `stream`, no host
+ * synchronisation.  SURFHIP_ERR_INVALID as surfhip_match_batch, and for a
+ * NULL or misaligned d_scratch with npairs > 0; npairs == 0 returns
+ * SURFHIP_OK without touching the GPU. */
+size_t surfhip_match_batch_cross_scratch(int npairs, int slots1, int slots2);
+int surfhip_match_batch_cross(surfhip_point* d_pts1, const float* d_desc1, const int* d_counts1, int slots1,
+                              const surfhip_point* d_pts2, const float* d_desc2, const int* d_counts2, int slots2,
+                              int npairs, int nfeatures, int flags, void* d_scratch, void* stream);
 
 /* ---------------------------------------------------------- homography --
  * Batched RANSAC homographies (no reference counterpart: main.cpp:250-262

@@ -9,7 +9,9 @@ matches pass the ambiguity filter; the stage is therefore also timed with
 the filter wide open (every matched point a candidate), its heaviest load.
 Prints one JSON line with the times in ms (median and range over --reps).
 
-    python tools/homography_bench.py [--batch 256] [--width 1920] [--height 1080] [--reps 7]
+--cross feeds it from surfhip_match_batch_cross (the mutual-best test) instead.
+
+    python tools/homography_bench.py [--batch 256] [--width 1920] [--height 1080] [--reps 7] [--cross]
 """
 from __future__ import annotations
 
@@ -46,6 +48,8 @@ def main():
     ap.add_argument("--inlier-thresh", type=float, default=3.0)
     ap.add_argument("--reps", type=int, default=7, help="timed repeats of each stage")
     ap.add_argument("--inner", type=int, default=4, help="calls per timed window")
+    ap.add_argument("--cross", action="store_true",
+                    help="match with surfhip_match_batch_cross (the mutual-best test) instead of surfhip_match_batch")
     args = ap.parse_args()
     import torch                      # first: its HIP runtime is the one copy in this process
     surf = load_surf()
@@ -71,10 +75,16 @@ def main():
         det.detect_batch(d_frames.data_ptr(), B, pitch, H * pitch, d_pts.data_ptr(), d_desc.data_ptr(),
                          d_cnt.data_ptr())
 
+    d_scratch = torch.empty(surf.match_batch_cross_scratch_bytes(npairs, slots, slots) if args.cross else 16,
+                            dtype=torch.uint8, device=dev)
+
     def match():
-        surf.match_batch(d_pts.data_ptr(), d_desc.data_ptr(), d_cnt.data_ptr(), slots,
-                         d_pts.data_ptr() + 48 * slots, d_desc.data_ptr() + 4 * slots * nf, d_cnt.data_ptr() + 4,
-                         slots, npairs, nf, 0, stream)
+        sets = (d_pts.data_ptr(), d_desc.data_ptr(), d_cnt.data_ptr(), slots,
+                d_pts.data_ptr() + 48 * slots, d_desc.data_ptr() + 4 * slots * nf, d_cnt.data_ptr() + 4, slots)
+        if args.cross:
+            surf.match_batch_cross(*sets, npairs, nf, d_scratch.data_ptr(), 0, stream)
+        else:
+            surf.match_batch(*sets, npairs, nf, 0, stream)
 
     def homography(max_ambiguity=args.max_ambiguity, out=d_out):
         surf.homography_batch(d_pts.data_ptr(), d_cnt.data_ptr(), slots, npairs, out.data_ptr(),
@@ -106,7 +116,8 @@ def main():
     counts = d_cnt.cpu().numpy()
     same = res.tobytes() == first.tobytes()
     out = {"case": f"{npairs} consecutive pairs of {B} {W}x{H} frames, nhyp {args.nhyp}, "
-                   f"ambiguity <= {args.max_ambiguity}, {args.inlier_thresh} px",
+                   f"ambiguity <= {args.max_ambiguity}, {args.inlier_thresh} px"
+                   + (", mutual-best matches" if args.cross else ""),
            "reps": args.reps, "inner": args.inner, "run_to_run_identical": same,
            "keypoints_mean": round(float(counts.mean()), 1), "keypoints_max": int(counts.max()),
            "ncand_mean": round(float(res["ncand"].mean()), 1), "ncand_max": int(res["ncand"].max()),
