@@ -136,6 +136,8 @@ _sigs = {
     "surfhip_match_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "surfhip_match_batch_cross_scratch": (_sz, [_i, _i, _i]),
     "surfhip_match_batch_cross": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "surfhip_match_batch_window_scratch": (_sz, [_i, _i, _i, _i]),
+    "surfhip_match_batch_window": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "surfhip_homography_batch": (_i, [_vp, _vp, _i, _i, C.c_float, C.c_float, _i, C.c_uint32, _vp, _vp, _vp]),
     "surfhip_homography_lds_capacity": (_i, []),
     "surfhip_ingest_create": (_i, [C.POINTER(_vp), _vp, _i]),
@@ -643,6 +645,35 @@ def match_batch_cross(pts1_ptr: int, desc1_ptr: int, counts1_ptr: int, slots1: i
     check(_lib.surfhip_match_batch_cross(pts1_ptr, desc1_ptr, counts1_ptr, slots1, pts2_ptr, desc2_ptr, counts2_ptr,
                                          slots2, npairs, nfeatures, flags, scratch_ptr, stream),
           "surfhip_match_batch_cross")
+
+
+MATCH_MUTUAL = 4            # match_batch_window only
+
+
+class MatchWindow(C.Structure):
+    """surfhip_match_window: a set-2 point is offered to a set-1 point when
+    dx_min <= x2 - x1 <= dx_max and dy_min <= y2 - y1 <= dy_max."""
+    _fields_ = [("dx_min", C.c_float), ("dx_max", C.c_float), ("dy_min", C.c_float), ("dy_max", C.c_float)]
+
+
+def match_batch_window_scratch_bytes(npairs: int, slots1: int, slots2: int, flags: int = 0) -> int:
+    return int(_lib.surfhip_match_batch_window_scratch(npairs, slots1, slots2, flags))
+
+
+def match_batch_window(pts1_ptr: int, desc1_ptr: int, counts1_ptr: int, slots1: int, pts2_ptr: int, desc2_ptr: int,
+                       counts2_ptr: int, slots2: int, npairs: int, nfeatures: int, flags: int, window,
+                       scratch_ptr: int, stream=None) -> None:
+    """surfhip_match_batch_window: match_batch over the set-2 points inside a
+    search window around each set-1 point (window: a MatchWindow or a
+    (dx_min, dx_max, dy_min, dy_max) tuple; infinite bounds are allowed),
+    with MATCH_MUTUAL in flags also the mutual-best test of match_batch_cross.
+    scratch_ptr: match_batch_window_scratch_bytes(...) of device memory in any
+    state."""
+    if not isinstance(window, MatchWindow):
+        window = MatchWindow(*window)
+    check(_lib.surfhip_match_batch_window(pts1_ptr, desc1_ptr, counts1_ptr, slots1, pts2_ptr, desc2_ptr,
+                                          counts2_ptr, slots2, npairs, nfeatures, flags, C.byref(window),
+                                          scratch_ptr, stream), "surfhip_match_batch_window")
 
 
 # ------------------------------------------------------------ homography

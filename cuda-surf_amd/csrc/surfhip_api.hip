@@ -1221,6 +1221,31 @@ int surfhip_match_batch_cross(surfhip_point* pts1, const float* f1, const int* c
     return SURFHIP_OK;
 }
 
+size_t surfhip_match_batch_window_scratch(int npairs, int slots1, int slots2, int flags)
+{
+    if (npairs <= 0 || slots1 <= 0 || slots2 <= 0) return 0;
+    return match_batch_window_scratch_bytes(npairs, slots2, flags);
+}
+
+int surfhip_match_batch_window(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
+                               const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
+                               int npairs, int nf, int flags, const surfhip_match_window* window, void* scratch,
+                               void* stream)
+{
+    if (npairs < 0 || slots1 <= 0 || slots2 <= 0 || nf < 4 || nf > 1024 || (nf & 3) ||
+        (flags & ~(SURFHIP_MATCH_FULL_TAIL | SURFHIP_MATCH_SAME_LAPLACE | SURFHIP_MATCH_MUTUAL)))
+        return SURFHIP_ERR_INVALID;
+    // (a NaN bound fails its comparison)
+    if (!window || !(window->dx_min <= window->dx_max) || !(window->dy_min <= window->dy_max))
+        return SURFHIP_ERR_INVALID;
+    if (npairs == 0) return SURFHIP_OK;
+    if (!pts1 || !f1 || !counts1 || !pts2 || !f2 || !counts2 || !scratch || ((uintptr_t)scratch & 15))
+        return SURFHIP_ERR_INVALID;
+    HIPCHK(launch_match_batch_window(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf, flags, *window,
+                                     scratch, (hipStream_t)stream));
+    return SURFHIP_OK;
+}
+
 static_assert(sizeof(surfhip_homography) == 64, "surfhip_homography is 64 bytes");
 
 int surfhip_homography_batch(const surfhip_point* pts1, const int* counts1, int slots1, int npairs,

@@ -289,6 +289,15 @@ size_t match_batch_cross_scratch_bytes(int npairs, int slots2);
 hipError_t launch_match_batch_cross(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
                                     const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
                                     int npairs, int nf, int flags, void* scratch, hipStream_t s);
+// Batched matching inside a search window (flags may carry
+// SURFHIP_MATCH_MUTUAL: then with the mutual-best filter).  scratch:
+// match_batch_window_scratch_bytes() of device memory in any state (16 B per
+// 32 set-2 slots for the tile boxes, then the mutual test's keys).
+size_t match_batch_window_scratch_bytes(int npairs, int slots2, int flags);
+hipError_t launch_match_batch_window(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
+                                     const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
+                                     int npairs, int nf, int flags, const surfhip_match_window& win, void* scratch,
+                                     hipStream_t s);
 // Batched RANSAC homographies (surfhip_homography.hip): one workgroup per
 // pair on the match fields of its set-1 points; kHomogCap candidates per
 // pair stay in LDS, more are re-read from the point array.

@@ -56,6 +56,17 @@
 // atomic max per (block, p2) to a caller-provided word per set-2 slot -- no
 // second score pass, and an integer maximum does not depend on arrival
 // order.  k_match_cross_filter then clears the matches that are not mutual.
+//
+// Windowed matching (surfhip_match_batch_window) offers p2 to p1 only inside
+// a search window around p1.  surfhip_detect_batch writes keypoints in the
+// order octave, level, row, column, so 32 consecutive points cover a narrow
+// band of rows: k_match_tile_boxes writes the bounding box of every set-2
+// tile, and the WIN instantiations of the batch kernels run their loop over
+// the tiles whose box can hold a partner of the block's points (a wave skips
+// the MFMAs of the tiles that cannot hold one of its own 32), with the window
+// test beside the Laplace test in the scan.  A skipped tile holds no offered
+// pair, so the result does not depend on the order of the points; the speed
+// does.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -241,13 +252,27 @@ __device__ __forceinline__ int clamp_count(int c, int slots) { return c < 0 ? 0 
 // CROSS: ks[4 q + r] also gets the score's bits where the pair (p1, p2) counts
 // for the back direction (p2 offered, p1 live, score > 0 -- never a NaN), 0
 // elsewhere; positive floats order like their bits.
-template <bool LAP, bool CROSS = false>
+// WIN (surfhip_match_batch_window): the pair also has to lie in the search
+// window w around the lane's point (x1, y1).  WIN_LDS: xy2 holds the tile's
+// 32 x then 32 y (16-B aligned), a lane reads its four positions of a q at
+// once; WIN_SHFL: x2, y2 are those of tile position (lane & 31).  A NaN
+// difference fails every comparison: not offered.
+enum { WIN_OFF = 0, WIN_LDS = 1, WIN_SHFL = 2 };
+
+template <bool LAP, bool CROSS = false, int WIN = WIN_OFF>
 __device__ __forceinline__ void scan_tile(const f32x16& acc, int t, int h, int nscan, int lap1, int lap2,
                                           float (&mx)[4], float (&sc)[4], int (&ix)[4], bool live1 = false,
-                                          uint32_t* ks = nullptr)
+                                          uint32_t* ks = nullptr, const surfhip_match_window* w = nullptr,
+                                          float x1 = 0.0f, float y1 = 0.0f, const float* xy2 = nullptr,
+                                          float x2 = 0.0f, float y2 = 0.0f)
 {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
+        float4 qx = {0, 0, 0, 0}, qy = {0, 0, 0, 0};
+        if constexpr (WIN == WIN_LDS) {
+            qx = *reinterpret_cast<const float4*>(xy2 + 8 * q + 4 * h);
+            qy = *reinterpret_cast<const float4*>(xy2 + 32 + 8 * q + 4 * h);
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int j = 8 * q + 4 * h + r;
@@ -256,6 +281,13 @@ __device__ __forceinline__ void scan_tile(const f32x16& acc, int t, int h, int n
             if (LAP) {
                 const int l2 = __shfl(lap2, j);
                 ok = ok && l2 == lap1;
+            }
+            if constexpr (WIN != WIN_OFF) {
+                const float xr = r == 0 ? qx.x : r == 1 ? qx.y : r == 2 ? qx.z : qx.w;
+                const float yr = r == 0 ? qy.x : r == 1 ? qy.y : r == 2 ? qy.z : qy.w;
+                const float dx = (WIN == WIN_LDS ? xr : __shfl(x2, j)) - x1;
+                const float dy = (WIN == WIN_LDS ? yr : __shfl(y2, j)) - y1;
+                ok = ok && dx >= w->dx_min && dx <= w->dx_max && dy >= w->dy_min && dy <= w->dy_max;
             }
             if (ok) scan_update(acc[4 * q + r], p2, mx[q], sc[q], ix[q]);
             if constexpr (CROSS) {
@@ -358,20 +390,84 @@ __device__ __forceinline__ void batch_finish(surfhip_point* pts1, const surfhip_
     q.ambiguity = S / (M + 1e-6f);
 }
 
+// ---- windowed matching: boxes --------------------------------------------
+// A box is (xmin, xmax, ymin, ymax) of some points' finite-or-infinite
+// coordinates; fminf / fmaxf drop NaN, and a box of no point is
+// (+inf, -inf, +inf, -inf).
+constexpr int kWinChunk = kBatchThreads;            // tile boxes a block tests at a time, one per thread
+
+// The box of the points of 32 consecutive lanes (x, y; live: the lane has
+// one), on every one of those lanes.
+__device__ __forceinline__ float4 box_of_32(float x, float y, bool live)
+{
+    const float inf = __builtin_inff(), nan = __builtin_nanf("");
+    x = live ? x : nan;
+    y = live ? y : nan;
+    float4 b = make_float4(fminf(inf, x), fmaxf(-inf, x), fminf(inf, y), fmaxf(-inf, y));
+#pragma unroll
+    for (int m = 1; m < 32; m <<= 1) {
+        b.x = fminf(b.x, __shfl_xor(b.x, m));
+        b.y = fmaxf(b.y, __shfl_xor(b.y, m));
+        b.z = fminf(b.z, __shfl_xor(b.z, m));
+        b.w = fmaxf(b.w, __shfl_xor(b.w, m));
+    }
+    return b;
+}
+
+__device__ __forceinline__ float4 box_union(const float4& a, const float4& b)
+{
+    return make_float4(fminf(a.x, b.x), fmaxf(a.y, b.y), fminf(a.z, b.z), fmaxf(a.w, b.w));
+}
+
+// May a set-1 point of box a be offered a set-2 point of box b?  Never false
+// for boxes that hold an offered pair: x2 - x1 lies between the two
+// differences tested here and fp32 subtraction is monotone; a NaN (inf - inf)
+// fails both comparisons, which keeps the tile.
+__device__ __forceinline__ bool box_may_offer(const float4& a, const float4& b, const surfhip_match_window& w)
+{
+    return !(b.x - a.y > w.dx_max) && !(b.y - a.x < w.dx_min) && !(b.z - a.w > w.dy_max) &&
+           !(b.w - a.z < w.dy_min);
+}
+
+// boxes[pair][tiles]: the box of every scanned 32-point tile of set 2 (the
+// tiles at or past ntile are not written and not read).
+__global__ __launch_bounds__(256) void k_match_tile_boxes(const surfhip_point* pts2, const int* __restrict__ counts2,
+                                                          int slots2, int full_tail, int tiles,
+                                                          float4* __restrict__ boxes)
+{
+    const int pair = blockIdx.y;
+    const int n2 = clamp_count(counts2[pair], slots2);
+    const int nscan = full_tail ? n2 : 32 * (n2 / 32);
+    const int t = blockIdx.x * 8 + (threadIdx.x >> 5);
+    const int p2 = 32 * t + (threadIdx.x & 31);
+    const bool live = p2 < nscan;
+    const surfhip_point* q = pts2 + (size_t)pair * slots2 + (live ? p2 : 0);
+    const float4 b = box_of_32(q->x, q->y, live);
+    if ((threadIdx.x & 31) == 0 && 32 * t < nscan) boxes[(size_t)pair * tiles + t] = b;
+}
+
 // pts1 / pts2 may overlap (consecutive frames of one batch): no __restrict__
 // on them; only the five match fields of pts1 are written and only x, y,
-// laplace of pts2 are read.
+// laplace of pts2 (WIN: and x, y of pts1) are read.
 // CROSS (surfhip_match_batch_cross): the tile's column maxima, which the
 // forward scan throws away, also go to back[pair][p2] as keys: the four
 // waves' maxima meet in LDS (ds_max_u64), and one tile later wave 0 sends the
 // block's 32 keys with one 256-B atomic-max instruction.
-template <int NF, bool LAP, bool CROSS>
+// WIN (surfhip_match_batch_window): the block keeps, in ascending order, the
+// tiles whose box (boxes[pair][tiles], k_match_tile_boxes) can hold a partner
+// of one of its live points, and runs the same loop over that list; a wave
+// whose own 32 points cannot have one in the staged tile only stages and
+// waits.  A skipped tile holds no offered pair, so no row state, no key and
+// no bit of the result depends on the skipping.
+template <int NF, bool LAP, bool CROSS, bool WIN = false>
 __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pts1, const float* __restrict__ f1,
                                                                const int* __restrict__ counts1, int slots1,
                                                                const surfhip_point* pts2,
                                                                const float* __restrict__ f2,
                                                                const int* __restrict__ counts2, int slots2,
-                                                               int full_tail, u64* __restrict__ back)
+                                                               int full_tail, u64* __restrict__ back,
+                                                               const float4* __restrict__ boxes, int tiles,
+                                                               surfhip_match_window win)
 {
     constexpr int RS = NF + 4;                              // LDS row: NF / 2 even, NF / 2 odd elements, pad
     constexpr int C4 = NF / 4;                              // float4 per descriptor
@@ -379,10 +475,22 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pt
     static_assert(32 * C4 % kBatchThreads == 0, "tile staging");
     __shared__ __attribute__((aligned(16))) float tile[2][32 * RS];
     __shared__ u64 colmax[CROSS ? 2 : 1][32];               // CROSS: the block's keys of tiles t and t + 1
+    // WIN: the staged tiles' x[32], y[32]; the waves' boxes and kept-tile
+    // counts; one chunk of the kept-tile list with the tiles' boxes
+    __shared__ __attribute__((aligned(16))) float xy2[WIN ? 2 : 1][64];
+    __shared__ float4 wbox[WIN ? kBatchWaves : 1];
+    __shared__ int wcnt[WIN ? kBatchWaves : 1];
+    __shared__ int tlist[WIN ? kWinChunk : 1];
+    __shared__ float4 tbox[WIN ? kWinChunk : 1];
 
     const int pair = blockIdx.y;
     const int n1 = clamp_count(counts1[pair], slots1);
-    const int base = blockIdx.x * kBatchPts;
+    // WIN: workgroups go to the 8 XCDs round-robin by their linear index, and
+    // with an even grid.x the blocks that keep most tiles (the small, tall
+    // (octave, level) groups at the end of every frame) would all meet on the
+    // same XCDs: rotate the point blocks by the pair
+    const int bx = WIN ? (blockIdx.x + blockIdx.y) % gridDim.x : blockIdx.x;
+    const int base = bx * kBatchPts;
     if (base >= n1) return;
     const int n2 = clamp_count(counts2[pair], slots2);
     const int nscan = full_tail ? n2 : 32 * (n2 / 32);
@@ -422,6 +530,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pt
 
     float4 v[NV];
     int lap2 = 0, lapn = 0;
+    float xn = 0.0f, yn = 0.0f;                             // WIN: x, y of the prefetched tile's position c
     auto load_tile = [&](int t) {
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
@@ -431,6 +540,10 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pt
             v[i] = reinterpret_cast<const float4*>(f2 + (size_t)p2 * NF)[col];
         }
         if (LAP) lapn = pts2[min(32 * t + c, nscan - 1)].laplace;
+        if constexpr (WIN) {
+            xn = pts2[min(32 * t + c, nscan - 1)].x;
+            yn = pts2[min(32 * t + c, nscan - 1)].y;
+        }
     };
     auto store_tile = [&](int buf) {
 #pragma unroll
@@ -441,15 +554,37 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pt
             *reinterpret_cast<float2*>(dst) = make_float2(v[i].x, v[i].z);
             *reinterpret_cast<float2*>(dst + NF / 2) = make_float2(v[i].y, v[i].w);
         }
+        if constexpr (WIN) {
+            if (tid < 32) {
+                xy2[buf][tid] = xn;
+                xy2[buf][32 + tid] = yn;
+            }
+        }
+    };
+    // WIN: the score tile D[p2][p1] of the wave's points against the staged
+    // tile (the WIN = false loop spells the same out: through this lambda its
+    // registers are allocated differently, and its code is meant to stay put)
+    auto score_tile = [&](int buf) {
+        const float4* ap = reinterpret_cast<const float4*>(&tile[buf][c * RS + h * (NF / 2)]);
+        f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < NF / 8; ++k) {
+            const float4 a = ap[k];
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b[4 * k], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b[4 * k + 1], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b[4 * k + 2], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b[4 * k + 3], acc, 0, 0, 0);
+        }
+        return acc;
     };
 
-    // CROSS: tile u's keys leave colmax[u & 1], which is zero again for tile
-    // u + 2 (a key of 0 is "none": nothing to send, and a sent key has
-    // 32 u + lane < nscan)
-    auto send_keys = [&](int u) {
+    // CROSS: the keys of tile u, the slot-th of the loop, leave colmax[slot & 1],
+    // which is zero again two tiles on (a key of 0 is "none": nothing to send,
+    // and a sent key has 32 u + lane < nscan)
+    auto send_keys = [&](int slot, int u) {
         if (tid < 32) {
-            const u64 key = colmax[u & 1][tid];
-            colmax[u & 1][tid] = 0;
+            const u64 key = colmax[slot & 1][tid];
+            colmax[slot & 1][tid] = 0;
             if (key) __hip_atomic_fetch_max(back + 32 * u + tid, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     };
@@ -457,52 +592,133 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pt
         if (tid < 64) colmax[tid >> 5][tid & 31] = 0;
     }
 
-    if (ntile > 0) {
-        load_tile(0);
-        store_tile(0);
-        lap2 = lapn;
-    }
-    __syncthreads();
-    for (int t = 0; t < ntile; ++t) {
-        const int cur = t & 1;
-        const bool more = t + 1 < ntile;
-        // unconditional (rows are clamped to valid ones; the last prefetch is
-        // unused): in a branch the loads' wait would end that branch, ahead
-        // of the MFMAs they are meant to run under
-        load_tile(t + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (CROSS) {
-            if (wave == 0 && t > 0) send_keys(t - 1);       // ahead of the MFMAs, which cover the atomics' latency
+    if constexpr (!WIN) {
+        if (ntile > 0) {
+            load_tile(0);
+            store_tile(0);
+            lap2 = lapn;
         }
-        if (wlive) {
-            const float4* ap = reinterpret_cast<const float4*>(&tile[cur][c * RS + h * (NF / 2)]);
-            f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        __syncthreads();
+        for (int t = 0; t < ntile; ++t) {
+            const int cur = t & 1;
+            const bool more = t + 1 < ntile;
+            // unconditional (rows are clamped to valid ones; the last prefetch is
+            // unused): in a branch the loads' wait would end that branch, ahead
+            // of the MFMAs they are meant to run under
+            load_tile(t + 1);
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (CROSS) {
+                // ahead of the MFMAs, which cover the atomics' latency
+                if (wave == 0 && t > 0) send_keys(t - 1, t - 1);
+            }
+            if (wlive) {
+                const float4* ap = reinterpret_cast<const float4*>(&tile[cur][c * RS + h * (NF / 2)]);
+                f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-            for (int k = 0; k < NF / 8; ++k) {
-                const float4 a = ap[k];
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b[4 * k], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b[4 * k + 1], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b[4 * k + 2], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b[4 * k + 3], acc, 0, 0, 0);
+                for (int k = 0; k < NF / 8; ++k) {
+                    const float4 a = ap[k];
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b[4 * k], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b[4 * k + 1], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b[4 * k + 2], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b[4 * k + 3], acc, 0, 0, 0);
+                }
+                if constexpr (CROSS) {
+                    uint32_t ks[16];
+                    scan_tile<LAP, true>(acc, t, h, nscan, lap1, lap2, mx, sc, ix, p1 < n1, ks);
+                    int j;
+                    const u64 key = cross_reduce(ks, p1, h, c, j);
+                    if (c < 16 && key)
+                        __hip_atomic_fetch_max(&colmax[cur][j], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                } else {
+                    scan_tile<LAP>(acc, t, h, nscan, lap1, lap2, mx, sc, ix);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (more) store_tile(cur ^ 1);
+            lap2 = lapn;
+            __syncthreads();
+        }
+        if constexpr (CROSS) {
+            if (wave == 0 && ntile > 0) send_keys(ntile - 1, ntile - 1);
+        }
+    } else {
+        boxes += (size_t)pair * tiles;
+        const float x1 = pts1[q1].x, y1 = pts1[q1].y;
+        const float4 mybox = box_of_32(x1, y1, p1 < n1);    // the wave's live points (none: a dead wave)
+        if (lane == 0) wbox[wave] = mybox;
+        __syncthreads();
+        float4 blockbox = wbox[0];
+#pragma unroll
+        for (int w = 1; w < kBatchWaves; ++w) blockbox = box_union(blockbox, wbox[w]);
+
+        for (int t0 = 0; t0 < ntile; t0 += kWinChunk) {
+            // the kept tiles of [t0, t0 + kWinChunk), ascending: thread tid
+            // tests tile t0 + tid, ballots and the waves' counts place it
+            const int tt = t0 + tid;
+            const float4 bb = boxes[min(tt, ntile - 1)];
+            const bool keep = tt < ntile && box_may_offer(blockbox, bb, win);
+            const u64 kept = __ballot(keep);
+            if (lane == 0) wcnt[wave] = __popcll(kept);
+            __syncthreads();
+            int first = 0, nl = 0;
+#pragma unroll
+            for (int w = 0; w < kBatchWaves; ++w) {
+                const int n = wcnt[w];
+                first += w < wave ? n : 0;
+                nl += n;
+            }
+            if (keep) {
+                const int pos = first + __popcll(kept & ((1ull << lane) - 1));
+                tlist[pos] = tt;
+                tbox[pos] = bb;
+            }
+            __syncthreads();
+            nl = __builtin_amdgcn_readfirstlane(nl);
+
+            // the loop above over the list; its tiles' keys leave before the
+            // next chunk's barriers, so both colmax slots are zero again there
+            if (nl > 0) {
+                load_tile(__builtin_amdgcn_readfirstlane(tlist[0]));
+                store_tile(0);
+                lap2 = lapn;
+            }
+            __syncthreads();
+            for (int i = 0; i < nl; ++i) {
+                const int cur = i & 1;
+                const bool more = i + 1 < nl;
+                const int t = __builtin_amdgcn_readfirstlane(tlist[i]);
+                load_tile(__builtin_amdgcn_readfirstlane(tlist[more ? i + 1 : i]));
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (CROSS) {
+                    if (wave == 0 && i > 0) send_keys(i - 1, __builtin_amdgcn_readfirstlane(tlist[i - 1]));
+                }
+                // the wave's own box: a block over two (octave, level) groups is
+                // tall, its waves are not
+                if (wlive && __builtin_amdgcn_readfirstlane(box_may_offer(mybox, tbox[i], win))) {
+                    const f32x16 acc = score_tile(cur);
+                    if constexpr (CROSS) {
+                        uint32_t ks[16];
+                        scan_tile<LAP, true, WIN_LDS>(acc, t, h, nscan, lap1, lap2, mx, sc, ix, p1 < n1, ks, &win, x1,
+                                                      y1, xy2[cur]);
+                        int j;
+                        const u64 key = cross_reduce(ks, p1, h, c, j);
+                        if (c < 16 && key)
+                            __hip_atomic_fetch_max(&colmax[cur][j], key, __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_WORKGROUP);
+                    } else {
+                        scan_tile<LAP, false, WIN_LDS>(acc, t, h, nscan, lap1, lap2, mx, sc, ix, false, nullptr, &win,
+                                                       x1, y1, xy2[cur]);
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                if (more) store_tile(cur ^ 1);
+                lap2 = lapn;
+                __syncthreads();
             }
             if constexpr (CROSS) {
-                uint32_t ks[16];
-                scan_tile<LAP, true>(acc, t, h, nscan, lap1, lap2, mx, sc, ix, p1 < n1, ks);
-                int j;
-                const u64 key = cross_reduce(ks, p1, h, c, j);
-                if (c < 16 && key)
-                    __hip_atomic_fetch_max(&colmax[cur][j], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            } else {
-                scan_tile<LAP>(acc, t, h, nscan, lap1, lap2, mx, sc, ix);
+                if (wave == 0 && nl > 0) send_keys(nl - 1, __builtin_amdgcn_readfirstlane(tlist[nl - 1]));
             }
         }
-        __builtin_amdgcn_sched_barrier(0);
-        if (more) store_tile(cur ^ 1);
-        lap2 = lapn;
-        __syncthreads();
-    }
-    if constexpr (CROSS) {
-        if (wave == 0 && ntile > 0) send_keys(ntile - 1);
     }
     if (wlive) batch_finish(pts1, pts2, p1, n1, h, mx, sc, ix);
 }
@@ -510,19 +726,23 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pt
 // Any descriptor length (a multiple of 4, <= 1024): both operands come from
 // memory at every k-step; no LDS, so a wave past n1 exits at once.
 // CROSS: every wave sends its own 32 keys per tile.
-template <bool LAP, bool CROSS>
+// WIN: a wave walks all tile boxes and skips the tiles its own box misses.
+template <bool LAP, bool CROSS, bool WIN = false>
 __global__ __launch_bounds__(kBatchThreads) void k_match_batch_any(surfhip_point* pts1,
                                                                    const float* __restrict__ f1,
                                                                    const int* __restrict__ counts1, int slots1,
                                                                    const surfhip_point* pts2,
                                                                    const float* __restrict__ f2,
                                                                    const int* __restrict__ counts2, int slots2,
-                                                                   int nf, int full_tail, u64* __restrict__ back)
+                                                                   int nf, int full_tail, u64* __restrict__ back,
+                                                                   const float4* __restrict__ boxes, int tiles,
+                                                                   surfhip_match_window win)
 {
     const int pair = blockIdx.y;
     const int n1 = clamp_count(counts1[pair], slots1);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int base = blockIdx.x * kBatchPts + 32 * wave;
+    const int bx = WIN ? (blockIdx.x + blockIdx.y) % gridDim.x : blockIdx.x;    // (as in k_match_batch)
+    const int base = bx * kBatchPts + 32 * wave;
     if (base >= n1) return;
     const int n2 = clamp_count(counts2[pair], slots2);
     const int nscan = full_tail ? n2 : 32 * (n2 / 32);
@@ -545,21 +765,36 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch_any(surfhip_point
         sc[q] = 0.0f;
         ix[q] = -1;
     }
+    float x1 = 0.0f, y1 = 0.0f;
+    float4 mybox = {0, 0, 0, 0};
+    if constexpr (WIN) {
+        boxes += (size_t)pair * tiles;
+        x1 = pts1[q1].x;
+        y1 = pts1[q1].y;
+        mybox = box_of_32(x1, y1, p1 < n1);
+    }
+    constexpr int W = WIN ? WIN_SHFL : WIN_OFF;
     for (int t = 0; t < ntile; ++t) {
+        if constexpr (WIN) {
+            if (!__builtin_amdgcn_readfirstlane(box_may_offer(mybox, boxes[t], win))) continue;
+        }
         const int q2 = min(32 * t + c, nscan - 1);
         const float* r2 = f2 + (size_t)q2 * nf + h;
         const int lap2 = LAP ? pts2[q2].laplace : 0;
+        const float x2 = WIN ? pts2[q2].x : 0.0f, y2 = WIN ? pts2[q2].y : 0.0f;
         f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         for (int d = 0; d < nf; d += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(r2[d], r1[d], acc, 0, 0, 0);
         if constexpr (CROSS) {
             uint32_t ks[16];
-            scan_tile<LAP, true>(acc, t, h, nscan, lap1, lap2, mx, sc, ix, p1 < n1, ks);
+            scan_tile<LAP, true, W>(acc, t, h, nscan, lap1, lap2, mx, sc, ix, p1 < n1, ks, &win, x1, y1, nullptr, x2,
+                                    y2);
             int j;
             const u64 key = cross_reduce(ks, p1, h, c, j);
             if (c < 16 && key)                              // a key: 32 t + j < nscan
                 __hip_atomic_fetch_max(back + 32 * t + j, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else {
-            scan_tile<LAP>(acc, t, h, nscan, lap1, lap2, mx, sc, ix);
+            scan_tile<LAP, false, W>(acc, t, h, nscan, lap1, lap2, mx, sc, ix, false, nullptr, &win, x1, y1, nullptr,
+                                     x2, y2);
         }
     }
     batch_finish(pts1, pts2, p1, n1, h, mx, sc, ix);
@@ -617,31 +852,41 @@ hipError_t launch_match(surfhip_point* pts1, const surfhip_point* pts2, const fl
     return hipGetLastError();
 }
 
-template <bool LAP, bool CROSS>
+template <bool LAP, bool CROSS, bool WIN>
 static void launch_match_batch_lap(dim3 grid, surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
                                    const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
-                                   int nf, int full_tail, u64* back, hipStream_t s)
+                                   int nf, int full_tail, u64* back, const float4* boxes, int tiles,
+                                   const surfhip_match_window& win, hipStream_t s)
 {
     if (nf == 64)
-        k_match_batch<64, LAP, CROSS><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2, counts2,
-                                                                     slots2, full_tail, back);
+        k_match_batch<64, LAP, CROSS, WIN><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2,
+                                                                          counts2, slots2, full_tail, back, boxes,
+                                                                          tiles, win);
     else if (nf == 128)
-        k_match_batch<128, LAP, CROSS><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2, counts2,
-                                                                      slots2, full_tail, back);
+        k_match_batch<128, LAP, CROSS, WIN><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2,
+                                                                           counts2, slots2, full_tail, back, boxes,
+                                                                           tiles, win);
     else
-        k_match_batch_any<LAP, CROSS><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2, counts2,
-                                                                     slots2, nf, full_tail, back);
+        k_match_batch_any<LAP, CROSS, WIN><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2,
+                                                                          counts2, slots2, nf, full_tail, back,
+                                                                          boxes, tiles, win);
 }
+
+static int match_window_tiles(int slots2) { return (slots2 + 31) / 32; }
 
 // back == nullptr: the forward match alone.  Otherwise back[npairs][slots2]
 // keys, zero on entry, get the back direction's best and the filter pass
 // follows each launch (the kernel boundary makes the keys visible to it).
-template <bool CROSS>
+// WIN: boxes[npairs][match_window_tiles(slots2)] are written ahead of each
+// launch, in any state on entry.
+template <bool CROSS, bool WIN>
 static hipError_t launch_match_batch_pass(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
                                           const surfhip_point* pts2, const float* f2, const int* counts2,
-                                          int slots2, int npairs, int nf, int flags, u64* back, hipStream_t s)
+                                          int slots2, int npairs, int nf, int flags, u64* back, float4* boxes,
+                                          const surfhip_match_window& win, hipStream_t s)
 {
     const int full_tail = (flags & SURFHIP_MATCH_FULL_TAIL) ? 1 : 0;
+    const int tiles = match_window_tiles(slots2);
     constexpr int kMaxGridY = 65535;                        // one launch up to this many pairs
     for (int p0 = 0; p0 < npairs; p0 += kMaxGridY) {
         const int np = npairs - p0 < kMaxGridY ? npairs - p0 : kMaxGridY;
@@ -651,12 +896,18 @@ static hipError_t launch_match_batch_pass(surfhip_point* pts1, const float* f1, 
         const float* fa = f1 + (size_t)p0 * slots1 * nf;
         const float* fb = f2 + (size_t)p0 * slots2 * nf;
         u64* bk = CROSS ? back + (size_t)p0 * slots2 : nullptr;
+        float4* bx = WIN ? boxes + (size_t)p0 * tiles : nullptr;
+        if (WIN) {
+            k_match_tile_boxes<<<dim3((tiles + 7) / 8, np), 256, 0, s>>>(b, counts2 + p0, slots2, full_tail, tiles, bx);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
         if (flags & SURFHIP_MATCH_SAME_LAPLACE)
-            launch_match_batch_lap<true, CROSS>(grid, a, fa, counts1 + p0, slots1, b, fb, counts2 + p0, slots2, nf,
-                                                full_tail, bk, s);
+            launch_match_batch_lap<true, CROSS, WIN>(grid, a, fa, counts1 + p0, slots1, b, fb, counts2 + p0, slots2,
+                                                     nf, full_tail, bk, bx, tiles, win, s);
         else
-            launch_match_batch_lap<false, CROSS>(grid, a, fa, counts1 + p0, slots1, b, fb, counts2 + p0, slots2, nf,
-                                                 full_tail, bk, s);
+            launch_match_batch_lap<false, CROSS, WIN>(grid, a, fa, counts1 + p0, slots1, b, fb, counts2 + p0, slots2,
+                                                      nf, full_tail, bk, bx, tiles, win, s);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         if (CROSS) {
@@ -672,8 +923,8 @@ hipError_t launch_match_batch(surfhip_point* pts1, const float* f1, const int* c
                               const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
                               int npairs, int nf, int flags, hipStream_t s)
 {
-    return launch_match_batch_pass<false>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf, flags,
-                                          nullptr, s);
+    return launch_match_batch_pass<false, false>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf,
+                                                 flags, nullptr, nullptr, {}, s);
 }
 
 size_t match_batch_cross_scratch_bytes(int npairs, int slots2)
@@ -687,8 +938,38 @@ hipError_t launch_match_batch_cross(surfhip_point* pts1, const float* f1, const 
 {
     const hipError_t e = hipMemsetAsync(scratch, 0, match_batch_cross_scratch_bytes(npairs, slots2), s);
     if (e != hipSuccess) return e;
-    return launch_match_batch_pass<true>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf, flags,
-                                         static_cast<u64*>(scratch), s);
+    return launch_match_batch_pass<true, false>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf,
+                                                flags, static_cast<u64*>(scratch), nullptr, {}, s);
+}
+
+// Scratch of the windowed match: the tile boxes, 16 B per (pair, 32 slots of
+// set 2), then with SURFHIP_MATCH_MUTUAL the keys of the mutual-best test.
+static size_t match_window_box_bytes(int npairs, int slots2)
+{
+    return sizeof(float4) * (size_t)npairs * (size_t)match_window_tiles(slots2);
+}
+
+size_t match_batch_window_scratch_bytes(int npairs, int slots2, int flags)
+{
+    if (npairs <= 0 || slots2 <= 0) return 0;
+    return match_window_box_bytes(npairs, slots2) +
+           ((flags & SURFHIP_MATCH_MUTUAL) ? match_batch_cross_scratch_bytes(npairs, slots2) : 0);
+}
+
+hipError_t launch_match_batch_window(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
+                                     const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
+                                     int npairs, int nf, int flags, const surfhip_match_window& win, void* scratch,
+                                     hipStream_t s)
+{
+    float4* boxes = static_cast<float4*>(scratch);
+    if (!(flags & SURFHIP_MATCH_MUTUAL))
+        return launch_match_batch_pass<false, true>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf,
+                                                    flags, nullptr, boxes, win, s);
+    u64* back = reinterpret_cast<u64*>(static_cast<char*>(scratch) + match_window_box_bytes(npairs, slots2));
+    const hipError_t e = hipMemsetAsync(back, 0, match_batch_cross_scratch_bytes(npairs, slots2), s);
+    if (e != hipSuccess) return e;
+    return launch_match_batch_pass<true, true>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf,
+                                               flags, back, boxes, win, s);
 }
 
 }  // namespace surfhip

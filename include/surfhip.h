@@ -442,6 +442,53 @@ int surfhip_match_batch_cross(surfhip_point* d_pts1, const float* d_desc1, const
                               const surfhip_point* d_pts2, const float* d_desc2, const int* d_counts2, int slots2,
                               int npairs, int nfeatures, int flags, void* d_scratch, void* stream);
 
+/* Batched matching inside a search window (OpenCV users know it as windowed
+ * or guided matching): the layouts, count clamping, nfeatures rule and
+ * overlap rule of surfhip_match_batch, for callers that know where a partner
+ * can lie -- a tracker the largest motion between frames, a stereo caller the
+ * disparity range on (nearly) one row.  Set-2 point p2 is offered to set-1
+ * point p1 when
+ *   p2 < nscan (as for surfhip_match_batch_cross),
+ *   with SURFHIP_MATCH_SAME_LAPLACE their `laplace` fields are equal, and
+ *   dx_min <= x2 - x1 <= dx_max and dy_min <= y2 - y1 <= dy_max: each
+ *   difference one fp32 subtraction, all four comparisons inclusive.  A NaN
+ *   difference (a NaN coordinate, inf - inf) is not offered.
+ * A point that is not offered keeps its position in its 32-point tile.
+ *   forward  surfhip_match_batch's per-thread-row top-2 scan and row merge
+ *            over the offered points only, on the same k-ordered fp32 FMA
+ *            chains.  A point with nothing offered gets match = -1 and
+ *            score = match_x = match_y = ambiguity = 0.
+ *   with SURFHIP_MATCH_MUTUAL  the back direction B(p2) and the clearing
+ *            rule of surfhip_match_batch_cross, with this "offered".
+ * The window {-inf, +inf, -inf, +inf} gives, for finite coordinates, the
+ * bits of surfhip_match_batch, with SURFHIP_MATCH_MUTUAL those of
+ * surfhip_match_batch_cross.  Only the five match fields of set-1 points
+ * below n1 are written; x, y of set 1 and x, y, laplace of set 2 are read.
+ * surfhip_detect_batch writes keypoints in the order octave, level, row,
+ * column, so 32 consecutive points cover a narrow band of rows: the call
+ * skips the 32 x 32 score tiles in which no pair can be offered (that changes
+ * no bit of the result; with points in another order it skips less and is
+ * as right).
+ * window: host memory, read during the call.  d_scratch:
+ * surfhip_match_batch_window_scratch(npairs, slots1, slots2, flags) bytes of
+ * device memory, 16-B aligned, in any state on entry:
+ *   16 * npairs * ceil(slots2 / 32)   the set-2 tiles' bounding boxes
+ *   + 8 * npairs * slots2             with SURFHIP_MATCH_MUTUAL, the keys
+ * and 0 for non-positive npairs or slots.  Asynchronous on `stream`, no host
+ * synchronisation, no allocation.  SURFHIP_ERR_INVALID for everything
+ * surfhip_match_batch rejects (flag bits other than 1 | 2 | 4 here), a NULL
+ * window, a NaN bound or min > max on an axis (infinite bounds are allowed)
+ * -- these for npairs == 0 too -- and a NULL or misaligned d_scratch with
+ * npairs > 0; otherwise npairs == 0 returns SURFHIP_OK without touching the
+ * GPU. */
+typedef struct surfhip_match_window { float dx_min, dx_max, dy_min, dy_max; } surfhip_match_window;
+#define SURFHIP_MATCH_MUTUAL 4   /* surfhip_match_batch_window only */
+size_t surfhip_match_batch_window_scratch(int npairs, int slots1, int slots2, int flags);
+int surfhip_match_batch_window(surfhip_point* d_pts1, const float* d_desc1, const int* d_counts1, int slots1,
+                               const surfhip_point* d_pts2, const float* d_desc2, const int* d_counts2, int slots2,
+                               int npairs, int nfeatures, int flags, const surfhip_match_window* window,
+                               void* d_scratch, void* stream);
+
 /* ---------------------------------------------------------- homography --
  * Batched RANSAC homographies (no reference counterpart: main.cpp:250-262
  * only draws the matches): one 3 x 3 matrix per frame pair from the match

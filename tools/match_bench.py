@@ -18,6 +18,18 @@ batch call's fp32 TFLOP/s.
 surfhip_match_batch_cross call (the same match with the mutual-best test) on
 the same data, alternating in one run, and prints both medians with their
 ranges and the ratio cross / batch.
+
+--window R detects 256 synthetic 1920 x 1080 frames (random points have no
+canonical order and would show nothing) and matches the 255 consecutive pairs
+on the detector's buffers, alternating in one run: surfhip_match_batch,
+surfhip_match_batch_window with +-R px on both axes, with the infinite window
+and with a window that holds no pair (the box pre-pass, the list building and
+the launches alone).  It also prints the share of (128-point block, tile) and
+(wave, tile) combinations the box tests keep, computed in numpy from the
+downloaded points: the factor the kernel can at best reach.  --cross does the
+same against surfhip_match_batch_cross (SURFHIP_MATCH_MUTUAL).
+
+    python tools/match_bench.py --window 32 [--cross] [--reps 7] [--inner 4]
 """
 from __future__ import annotations
 
@@ -148,6 +160,122 @@ def bench_cross(surf, torch, npairs, n, reps, inner):
         del ft, pts, pts_c, scratch
 
 
+def kept_tile_shares(surf, pts, counts, win):
+    """The share of (128-point block, 32-point tile) and of (32-point wave,
+    tile) combinations of consecutive frame pairs that the windowed kernel's
+    fp32 box tests keep, computed from the downloaded points (flags 0: full
+    tiles only).  Random points would keep nearly all; detect_batch's order
+    (octave, level, row, column) is what makes the boxes narrow."""
+    w = np.asarray(win, np.float32)
+    inf = np.float32(np.inf)
+
+    def boxes(p, n, group):
+        g = (n + group - 1) // group
+        x = np.full(g * group, np.nan, np.float32)
+        y = np.full(g * group, np.nan, np.float32)
+        x[:n], y[:n] = p["x"][:n], p["y"][:n]
+        x, y = x.reshape(g, group), y.reshape(g, group)
+        return (np.fmin.reduce(x, axis=1, initial=inf), np.fmax.reduce(x, axis=1, initial=-inf),
+                np.fmin.reduce(y, axis=1, initial=inf), np.fmax.reduce(y, axis=1, initial=-inf))
+
+    tot = {128: 0, 32: 0}
+    kept = {128: 0, 32: 0}
+    for i in range(len(counts) - 1):
+        n1, nscan = int(counts[i]), 32 * (int(counts[i + 1]) // 32)
+        if n1 == 0 or nscan == 0:
+            continue
+        b = boxes(pts[i + 1], nscan, 32)
+        for group in (128, 32):
+            a = boxes(pts[i], n1, group)
+            with np.errstate(invalid="ignore"):
+                keep = (~(b[0][None] - a[1][:, None] > w[1]) & ~(b[1][None] - a[0][:, None] < w[0])
+                        & ~(b[2][None] - a[3][:, None] > w[3]) & ~(b[3][None] - a[2][:, None] < w[2]))
+            tot[group] += keep.size
+            kept[group] += int(keep.sum())
+    return kept[128] / max(tot[128], 1), kept[32] / max(tot[32], 1)
+
+
+def bench_window(surf, torch, radius, cross, frames_n, reps, inner, width=1920, height=1080, thresh=4.0,
+                 slots=8192):
+    """surfhip_match_batch (or, with cross, surfhip_match_batch_cross) against
+    surfhip_match_batch_window with +-radius px, with the infinite window and
+    with a window no pair lies in (the cost of the box pre-pass, the list
+    building and the launches), alternating in one run, on the consecutive
+    pairs of one detected batch of synthetic frames in the detector's own
+    buffers."""
+    dev = torch.device("cuda", 0)
+    surf.set_device(0)
+    B, npairs = frames_n, frames_n - 1
+    pitch = surf.align_up(width, 128)
+    d_frames = torch.from_numpy(surf.synth_frames(B, width, height, pitch)).to(dev)
+    param = surf.make_param(4, thresh, False, 9, 2, True, False, 4)
+    nf = param.nfeatures
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    det = surf.Detector(param, width, height, max_batch=B, max_pts=slots, stream=stream)
+    d_pts = torch.zeros(B * slots * 48, dtype=torch.uint8, device=dev)
+    d_desc = torch.empty(B * slots * nf, dtype=torch.float32, device=dev)
+    d_cnt = torch.zeros(B, dtype=torch.int32, device=dev)
+    det.detect_batch(d_frames.data_ptr(), B, pitch, height * pitch, d_pts.data_ptr(), d_desc.data_ptr(),
+                     d_cnt.data_ptr())
+    mutual = surf.MATCH_MUTUAL if cross else 0
+    d_scratch = torch.empty(max(surf.match_batch_window_scratch_bytes(npairs, slots, slots, mutual),
+                                surf.match_batch_cross_scratch_bytes(npairs, slots, slots), 16),
+                            dtype=torch.uint8, device=dev)
+    sets = (d_pts.data_ptr(), d_desc.data_ptr(), d_cnt.data_ptr(), slots,
+            d_pts.data_ptr() + 48 * slots, d_desc.data_ptr() + 4 * slots * nf, d_cnt.data_ptr() + 4, slots)
+    inf = float("inf")
+    windows = {"window": (-radius, radius, -radius, radius), "infinite": (-inf, inf, -inf, inf),
+               "empty": (1e30, 1e30, 1e30, 1e30)}
+
+    def plain():
+        if cross:
+            surf.match_batch_cross(*sets, npairs, nf, d_scratch.data_ptr(), 0, stream)
+        else:
+            surf.match_batch(*sets, npairs, nf, 0, stream)
+
+    def windowed(name):
+        return lambda: surf.match_batch_window(*sets, npairs, nf, mutual, windows[name], d_scratch.data_ptr(), stream)
+
+    calls = {"plain": plain, "window": windowed("window"), "infinite": windowed("infinite"),
+             "empty": windowed("empty")}
+    out = {}
+    for name, fn in calls.items():                  # warm-up, and the results to compare
+        fn()
+        torch.cuda.synchronize()
+        out[name] = d_pts.cpu().numpy().view(surf.POINT_DTYPE).reshape(B, slots).copy()
+    counts = d_cnt.cpu().numpy()
+    same = out["infinite"].tobytes() == out["plain"].tobytes()
+    times = {name: [] for name in calls}
+    for _ in range(reps):                           # the calls alternate inside one run
+        for name, fn in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(inner):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1) / inner)
+    block_share, wave_share = kept_tile_shares(surf, out["plain"], counts, windows["window"])
+    live = np.arange(slots)[None, :] < counts[:-1, None]
+    res = {"case": f"{npairs} consecutive pairs of {B} {width}x{height} frames, nf={nf} flags=0, "
+                   f"window +-{radius} px" + (", mutual-best" if cross else ""),
+           "reps": reps, "inner": inner, "keypoints_mean": round(float(counts.mean()), 1),
+           "keypoints_max": int(counts.max()),
+           "matches_plain": int((out["plain"]["match"][:-1][live] >= 0).sum()),
+           "matches_window": int((out["window"]["match"][:-1][live] >= 0).sum()),
+           "kept_block_tile_share": round(block_share, 4), "kept_wave_tile_share": round(wave_share, 4),
+           "infinite_window_bit_identical": same}
+    for name, t in times.items():
+        res[f"{name}_ms"] = round(float(np.median(t)), 4)
+        res[f"{name}_ms_range"] = [round(min(t), 4), round(max(t), 4)]
+    res["window_over_plain"] = round(res["window_ms"] / res["plain_ms"], 4)
+    res["infinite_over_plain"] = round(res["infinite_ms"] / res["plain_ms"], 4)
+    print(json.dumps(res), flush=True)
+    det.close()
+    if not same:
+        raise SystemExit("the infinite window disagrees with the unwindowed call")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=3000)
@@ -158,9 +286,15 @@ def main():
     ap.add_argument("--inner", type=int, default=4, help="--batch: batch calls per timed window")
     ap.add_argument("--cross", action="store_true",
                     help="--batch: time surfhip_match_batch against surfhip_match_batch_cross instead")
+    ap.add_argument("--window", type=float, default=0.0, metavar="R",
+                    help="time surfhip_match_batch_window with +-R px on detected frames (--cross: with MUTUAL)")
+    ap.add_argument("--frames", type=int, default=256, help="--window: synthetic 1920x1080 frames to detect")
     args = ap.parse_args()
     import torch
     surf = load_surf()
+    if args.window > 0:
+        bench_window(surf, torch, args.window, args.cross, args.frames, args.reps, args.inner)
+        return
     if args.batch > 0 and args.cross:
         bench_cross(surf, torch, args.batch, args.n, args.reps, args.inner)
         return
