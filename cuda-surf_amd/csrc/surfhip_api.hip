@@ -1246,7 +1246,33 @@ int surfhip_match_batch_window(surfhip_point* pts1, const float* f1, const int* 
     return SURFHIP_OK;
 }
 
+size_t surfhip_match_batch_guided_scratch(int npairs, int slots1, int slots2, int flags)
+{
+    return surfhip_match_batch_window_scratch(npairs, slots1, slots2, flags);
+}
+
+int surfhip_match_batch_guided(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
+                               const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
+                               int npairs, int nf, int flags, const float* h, int h_stride,
+                               const surfhip_match_window* window, void* scratch, void* stream)
+{
+    if (npairs < 0 || slots1 <= 0 || slots2 <= 0 || nf < 4 || nf > 1024 || (nf & 3) ||
+        (flags & ~(SURFHIP_MATCH_FULL_TAIL | SURFHIP_MATCH_SAME_LAPLACE | SURFHIP_MATCH_MUTUAL)))
+        return SURFHIP_ERR_INVALID;
+    if (!window || !(window->dx_min <= window->dx_max) || !(window->dy_min <= window->dy_max))
+        return SURFHIP_ERR_INVALID;
+    if (h_stride != 0 && h_stride < 9) return SURFHIP_ERR_INVALID;
+    if (npairs == 0) return SURFHIP_OK;
+    if (!pts1 || !f1 || !counts1 || !pts2 || !f2 || !counts2 || !scratch || ((uintptr_t)scratch & 15) || !h ||
+        ((uintptr_t)h & 3))
+        return SURFHIP_ERR_INVALID;
+    HIPCHK(launch_match_batch_guided(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf, flags, h,
+                                     h_stride, *window, scratch, (hipStream_t)stream));
+    return SURFHIP_OK;
+}
+
 static_assert(sizeof(surfhip_homography) == 64, "surfhip_homography is 64 bytes");
+static_assert(offsetof(surfhip_homography, h) == 0, "surfhip_match_batch_guided reads h at the record's start");
 
 int surfhip_homography_batch(const surfhip_point* pts1, const int* counts1, int slots1, int npairs,
                              float max_ambiguity, float inlier_thresh, int nhyp, uint32_t seed,

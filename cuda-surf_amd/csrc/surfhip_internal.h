@@ -298,6 +298,13 @@ hipError_t launch_match_batch_window(surfhip_point* pts1, const float* f1, const
                                      const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
                                      int npairs, int nf, int flags, const surfhip_match_window& win, void* scratch,
                                      hipStream_t s);
+// The same with the window measured from each set-1 point's predicted
+// position under its pair's 3 x 3 matrix: the nine row-major floats at
+// hm + i * h_stride in device memory, read in stream order.  Scratch as above.
+hipError_t launch_match_batch_guided(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
+                                     const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
+                                     int npairs, int nf, int flags, const float* hm, int h_stride,
+                                     const surfhip_match_window& win, void* scratch, hipStream_t s);
 // Batched RANSAC homographies (surfhip_homography.hip): one workgroup per
 // pair on the match fields of its set-1 points; kHomogCap candidates per
 // pair stay in LDS, more are re-read from the point array.

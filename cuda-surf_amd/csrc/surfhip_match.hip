@@ -67,6 +67,13 @@
 // test beside the Laplace test in the scan.  A skipped tile holds no offered
 // pair, so the result does not depend on the order of the points; the speed
 // does.
+//
+// Guided matching (surfhip_match_batch_guided) measures the window from the
+// point's predicted position H (x1, y1) instead, H the pair's 3 x 3 matrix in
+// device memory: the GUIDED instantiations project every set-1 point once,
+// ahead of the tile loop, and from there on the prediction (u, v) stands where
+// the window kernels have (x1, y1) -- in the boxes, the kept-tile list and the
+// scan's test.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -258,6 +265,24 @@ __device__ __forceinline__ int clamp_count(int c, int slots) { return c < 0 ? 0 
 // once; WIN_SHFL: x2, y2 are those of tile position (lane & 31).  A NaN
 // difference fails every comparison: not offered.
 enum { WIN_OFF = 0, WIN_LDS = 1, WIN_SHFL = 2 };
+
+// What a batch kernel offers: everything, a window around (x1, y1), or a
+// window around the prediction H (x1, y1).
+enum { MATCH_PLAIN = 0, MATCH_WINDOW = 1, MATCH_GUIDED = 2 };
+
+// The predicted position of (x, y) under the row-major 3 x 3 matrix m, in the
+// operation order of transfer_err2 (surfhip_homography.hip), one fp32
+// rounding per written operation and IEEE quotients.  W > 0 false (W <= 0 or
+// NaN): (NaN, NaN), which no window test and no box takes.
+__device__ __forceinline__ void guided_predict(const float* __restrict__ m, float x, float y, float& u, float& v)
+{
+    const float X = (m[0] * x + m[1] * y) + m[2];
+    const float Y = (m[3] * x + m[4] * y) + m[5];
+    const float W = (m[6] * x + m[7] * y) + m[8];
+    const bool front = W > 0.0f;
+    u = front ? X / W : __builtin_nanf("");
+    v = front ? Y / W : __builtin_nanf("");
+}
 
 template <bool LAP, bool CROSS = false, int WIN = WIN_OFF>
 __device__ __forceinline__ void scan_tile(const f32x16& acc, int t, int h, int nscan, int lap1, int lap2,
@@ -459,7 +484,9 @@ __global__ __launch_bounds__(256) void k_match_tile_boxes(const surfhip_point* p
 // whose own 32 points cannot have one in the staged tile only stages and
 // waits.  A skipped tile holds no offered pair, so no row state, no key and
 // no bit of the result depends on the skipping.
-template <int NF, bool LAP, bool CROSS, bool WIN = false>
+// GUIDED (surfhip_match_batch_guided): WIN around the lane's prediction under
+// the pair's matrix, the nine floats at hm + pair * h_stride.
+template <int NF, bool LAP, bool CROSS, int MODE = MATCH_PLAIN>
 __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pts1, const float* __restrict__ f1,
                                                                const int* __restrict__ counts1, int slots1,
                                                                const surfhip_point* pts2,
@@ -467,8 +494,10 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pt
                                                                const int* __restrict__ counts2, int slots2,
                                                                int full_tail, u64* __restrict__ back,
                                                                const float4* __restrict__ boxes, int tiles,
-                                                               surfhip_match_window win)
+                                                               surfhip_match_window win,
+                                                               const float* __restrict__ hm, int h_stride)
 {
+    constexpr bool WIN = MODE != MATCH_PLAIN;
     constexpr int RS = NF + 4;                              // LDS row: NF / 2 even, NF / 2 odd elements, pad
     constexpr int C4 = NF / 4;                              // float4 per descriptor
     constexpr int NV = 32 * C4 / kBatchThreads;             // float4 per thread per tile
@@ -643,7 +672,8 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pt
         }
     } else {
         boxes += (size_t)pair * tiles;
-        const float x1 = pts1[q1].x, y1 = pts1[q1].y;
+        float x1 = pts1[q1].x, y1 = pts1[q1].y;
+        if constexpr (MODE == MATCH_GUIDED) guided_predict(hm + (size_t)pair * h_stride, x1, y1, x1, y1);
         const float4 mybox = box_of_32(x1, y1, p1 < n1);    // the wave's live points (none: a dead wave)
         if (lane == 0) wbox[wave] = mybox;
         __syncthreads();
@@ -727,7 +757,8 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pt
 // memory at every k-step; no LDS, so a wave past n1 exits at once.
 // CROSS: every wave sends its own 32 keys per tile.
 // WIN: a wave walks all tile boxes and skips the tiles its own box misses.
-template <bool LAP, bool CROSS, bool WIN = false>
+// GUIDED: as in k_match_batch.
+template <bool LAP, bool CROSS, int MODE = MATCH_PLAIN>
 __global__ __launch_bounds__(kBatchThreads) void k_match_batch_any(surfhip_point* pts1,
                                                                    const float* __restrict__ f1,
                                                                    const int* __restrict__ counts1, int slots1,
@@ -736,8 +767,10 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch_any(surfhip_point
                                                                    const int* __restrict__ counts2, int slots2,
                                                                    int nf, int full_tail, u64* __restrict__ back,
                                                                    const float4* __restrict__ boxes, int tiles,
-                                                                   surfhip_match_window win)
+                                                                   surfhip_match_window win,
+                                                                   const float* __restrict__ hm, int h_stride)
 {
+    constexpr bool WIN = MODE != MATCH_PLAIN;
     const int pair = blockIdx.y;
     const int n1 = clamp_count(counts1[pair], slots1);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -771,6 +804,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch_any(surfhip_point
         boxes += (size_t)pair * tiles;
         x1 = pts1[q1].x;
         y1 = pts1[q1].y;
+        if constexpr (MODE == MATCH_GUIDED) guided_predict(hm + (size_t)pair * h_stride, x1, y1, x1, y1);
         mybox = box_of_32(x1, y1, p1 < n1);
     }
     constexpr int W = WIN ? WIN_SHFL : WIN_OFF;
@@ -852,24 +886,24 @@ hipError_t launch_match(surfhip_point* pts1, const surfhip_point* pts2, const fl
     return hipGetLastError();
 }
 
-template <bool LAP, bool CROSS, bool WIN>
+template <bool LAP, bool CROSS, int MODE>
 static void launch_match_batch_lap(dim3 grid, surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
                                    const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
                                    int nf, int full_tail, u64* back, const float4* boxes, int tiles,
-                                   const surfhip_match_window& win, hipStream_t s)
+                                   const surfhip_match_window& win, const float* hm, int h_stride, hipStream_t s)
 {
     if (nf == 64)
-        k_match_batch<64, LAP, CROSS, WIN><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2,
-                                                                          counts2, slots2, full_tail, back, boxes,
-                                                                          tiles, win);
-    else if (nf == 128)
-        k_match_batch<128, LAP, CROSS, WIN><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2,
+        k_match_batch<64, LAP, CROSS, MODE><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2,
                                                                            counts2, slots2, full_tail, back, boxes,
-                                                                           tiles, win);
+                                                                           tiles, win, hm, h_stride);
+    else if (nf == 128)
+        k_match_batch<128, LAP, CROSS, MODE><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2,
+                                                                            counts2, slots2, full_tail, back, boxes,
+                                                                            tiles, win, hm, h_stride);
     else
-        k_match_batch_any<LAP, CROSS, WIN><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2,
-                                                                          counts2, slots2, nf, full_tail, back,
-                                                                          boxes, tiles, win);
+        k_match_batch_any<LAP, CROSS, MODE><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2,
+                                                                           counts2, slots2, nf, full_tail, back,
+                                                                           boxes, tiles, win, hm, h_stride);
 }
 
 static int match_window_tiles(int slots2) { return (slots2 + 31) / 32; }
@@ -878,13 +912,16 @@ static int match_window_tiles(int slots2) { return (slots2 + 31) / 32; }
 // keys, zero on entry, get the back direction's best and the filter pass
 // follows each launch (the kernel boundary makes the keys visible to it).
 // WIN: boxes[npairs][match_window_tiles(slots2)] are written ahead of each
-// launch, in any state on entry.
-template <bool CROSS, bool WIN>
+// launch, in any state on entry.  GUIDED: pair i's matrix is the nine floats at
+// hm + i * h_stride (device memory).
+template <bool CROSS, int MODE>
 static hipError_t launch_match_batch_pass(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
                                           const surfhip_point* pts2, const float* f2, const int* counts2,
                                           int slots2, int npairs, int nf, int flags, u64* back, float4* boxes,
-                                          const surfhip_match_window& win, hipStream_t s)
+                                          const surfhip_match_window& win, const float* hm, int h_stride,
+                                          hipStream_t s)
 {
+    constexpr bool WIN = MODE != MATCH_PLAIN;
     const int full_tail = (flags & SURFHIP_MATCH_FULL_TAIL) ? 1 : 0;
     const int tiles = match_window_tiles(slots2);
     constexpr int kMaxGridY = 65535;                        // one launch up to this many pairs
@@ -897,17 +934,18 @@ static hipError_t launch_match_batch_pass(surfhip_point* pts1, const float* f1, 
         const float* fb = f2 + (size_t)p0 * slots2 * nf;
         u64* bk = CROSS ? back + (size_t)p0 * slots2 : nullptr;
         float4* bx = WIN ? boxes + (size_t)p0 * tiles : nullptr;
+        const float* hp = MODE == MATCH_GUIDED ? hm + (size_t)p0 * h_stride : nullptr;
         if (WIN) {
             k_match_tile_boxes<<<dim3((tiles + 7) / 8, np), 256, 0, s>>>(b, counts2 + p0, slots2, full_tail, tiles, bx);
             const hipError_t e = hipGetLastError();
             if (e != hipSuccess) return e;
         }
         if (flags & SURFHIP_MATCH_SAME_LAPLACE)
-            launch_match_batch_lap<true, CROSS, WIN>(grid, a, fa, counts1 + p0, slots1, b, fb, counts2 + p0, slots2,
-                                                     nf, full_tail, bk, bx, tiles, win, s);
+            launch_match_batch_lap<true, CROSS, MODE>(grid, a, fa, counts1 + p0, slots1, b, fb, counts2 + p0, slots2,
+                                                      nf, full_tail, bk, bx, tiles, win, hp, h_stride, s);
         else
-            launch_match_batch_lap<false, CROSS, WIN>(grid, a, fa, counts1 + p0, slots1, b, fb, counts2 + p0, slots2,
-                                                      nf, full_tail, bk, bx, tiles, win, s);
+            launch_match_batch_lap<false, CROSS, MODE>(grid, a, fa, counts1 + p0, slots1, b, fb, counts2 + p0, slots2,
+                                                       nf, full_tail, bk, bx, tiles, win, hp, h_stride, s);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         if (CROSS) {
@@ -923,8 +961,8 @@ hipError_t launch_match_batch(surfhip_point* pts1, const float* f1, const int* c
                               const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
                               int npairs, int nf, int flags, hipStream_t s)
 {
-    return launch_match_batch_pass<false, false>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf,
-                                                 flags, nullptr, nullptr, {}, s);
+    return launch_match_batch_pass<false, MATCH_PLAIN>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs,
+                                                       nf, flags, nullptr, nullptr, {}, nullptr, 0, s);
 }
 
 size_t match_batch_cross_scratch_bytes(int npairs, int slots2)
@@ -938,8 +976,9 @@ hipError_t launch_match_batch_cross(surfhip_point* pts1, const float* f1, const 
 {
     const hipError_t e = hipMemsetAsync(scratch, 0, match_batch_cross_scratch_bytes(npairs, slots2), s);
     if (e != hipSuccess) return e;
-    return launch_match_batch_pass<true, false>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf,
-                                                flags, static_cast<u64*>(scratch), nullptr, {}, s);
+    return launch_match_batch_pass<true, MATCH_PLAIN>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs,
+                                                      nf, flags, static_cast<u64*>(scratch), nullptr, {}, nullptr, 0,
+                                                      s);
 }
 
 // Scratch of the windowed match: the tile boxes, 16 B per (pair, 32 slots of
@@ -956,20 +995,40 @@ size_t match_batch_window_scratch_bytes(int npairs, int slots2, int flags)
            ((flags & SURFHIP_MATCH_MUTUAL) ? match_batch_cross_scratch_bytes(npairs, slots2) : 0);
 }
 
+// The windowed (hm == nullptr) and the guided match: one scratch layout.
+template <int MODE>
+static hipError_t launch_match_batch_boxed(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
+                                           const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
+                                           int npairs, int nf, int flags, const surfhip_match_window& win,
+                                           const float* hm, int h_stride, void* scratch, hipStream_t s)
+{
+    float4* boxes = static_cast<float4*>(scratch);
+    if (!(flags & SURFHIP_MATCH_MUTUAL))
+        return launch_match_batch_pass<false, MODE>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf,
+                                                    flags, nullptr, boxes, win, hm, h_stride, s);
+    u64* back = reinterpret_cast<u64*>(static_cast<char*>(scratch) + match_window_box_bytes(npairs, slots2));
+    const hipError_t e = hipMemsetAsync(back, 0, match_batch_cross_scratch_bytes(npairs, slots2), s);
+    if (e != hipSuccess) return e;
+    return launch_match_batch_pass<true, MODE>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf,
+                                               flags, back, boxes, win, hm, h_stride, s);
+}
+
 hipError_t launch_match_batch_window(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
                                      const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
                                      int npairs, int nf, int flags, const surfhip_match_window& win, void* scratch,
                                      hipStream_t s)
 {
-    float4* boxes = static_cast<float4*>(scratch);
-    if (!(flags & SURFHIP_MATCH_MUTUAL))
-        return launch_match_batch_pass<false, true>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf,
-                                                    flags, nullptr, boxes, win, s);
-    u64* back = reinterpret_cast<u64*>(static_cast<char*>(scratch) + match_window_box_bytes(npairs, slots2));
-    const hipError_t e = hipMemsetAsync(back, 0, match_batch_cross_scratch_bytes(npairs, slots2), s);
-    if (e != hipSuccess) return e;
-    return launch_match_batch_pass<true, true>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf,
-                                               flags, back, boxes, win, s);
+    return launch_match_batch_boxed<MATCH_WINDOW>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf,
+                                                  flags, win, nullptr, 0, scratch, s);
+}
+
+hipError_t launch_match_batch_guided(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
+                                     const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
+                                     int npairs, int nf, int flags, const float* hm, int h_stride,
+                                     const surfhip_match_window& win, void* scratch, hipStream_t s)
+{
+    return launch_match_batch_boxed<MATCH_GUIDED>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf,
+                                                  flags, win, hm, h_stride, scratch, s);
 }
 
 }  // namespace surfhip

@@ -482,12 +482,64 @@ int surfhip_match_batch_cross(surfhip_point* d_pts1, const float* d_desc1, const
  * npairs > 0; otherwise npairs == 0 returns SURFHIP_OK without touching the
  * GPU. */
 typedef struct surfhip_match_window { float dx_min, dx_max, dy_min, dy_max; } surfhip_match_window;
-#define SURFHIP_MATCH_MUTUAL 4   /* surfhip_match_batch_window only */
+#define SURFHIP_MATCH_MUTUAL 4   /* surfhip_match_batch_window and _guided only */
 size_t surfhip_match_batch_window_scratch(int npairs, int slots1, int slots2, int flags);
 int surfhip_match_batch_window(surfhip_point* d_pts1, const float* d_desc1, const int* d_counts1, int slots1,
                                const surfhip_point* d_pts2, const float* d_desc2, const int* d_counts2, int slots2,
                                int npairs, int nfeatures, int flags, const surfhip_match_window* window,
                                void* d_scratch, void* stream);
+
+/* Guided matching: surfhip_match_batch_window with the window measured from
+ * each set-1 point's predicted position under a per-pair 3 x 3 homography
+ * instead of from the point itself -- the second pass of a tracker whose
+ * camera pans, rolls or zooms: detect -> window match ->
+ * surfhip_homography_batch -> guided match inside a tight window, with the
+ * matrices never leaving the device.  Layouts, count clamping, flags
+ * (SURFHIP_MATCH_FULL_TAIL | SURFHIP_MATCH_SAME_LAPLACE | SURFHIP_MATCH_MUTUAL),
+ * the nfeatures rule, the overlap rule for consecutive frames and the scratch
+ * (layout and size: surfhip_match_batch_guided_scratch returns the numbers of
+ * surfhip_match_batch_window_scratch) are those of surfhip_match_batch_window.
+ * d_h: device memory, 4-byte aligned, read on the device in stream order, so
+ * the output of a surfhip_homography_batch enqueued earlier on the same
+ * stream can be passed directly.  Pair i uses the nine row-major floats at
+ * d_h + i * h_stride, h_stride in floats: 16 for an array of
+ * surfhip_homography (h is its first member; nothing else of the record is
+ * read, not even status: a TOO_FEW / DEGENERATE record holds the identity and
+ * so degrades to the plain window), 9 for packed matrices, any value >= 9, or
+ * 0 for one matrix shared by all pairs.
+ * Predicted position of (x1, y1), every written operation one fp32 rounding
+ * (the order of surfhip_homography_batch's transfer error) and the quotients
+ * IEEE:
+ *   X = (h0*x1 + h1*y1) + h2;  Y = (h3*x1 + h4*y1) + h5;  W = (h6*x1 + h7*y1) + h8;
+ *   u = X / W;  v = Y / W;
+ * Set-2 point p2 is offered to set-1 point p1 when W > 0, p2 < nscan, with
+ * SURFHIP_MATCH_SAME_LAPLACE their `laplace` fields are equal, and
+ * dx_min <= x2 - u <= dx_max and dy_min <= y2 - v <= dy_max: one fp32
+ * subtraction each, all comparisons inclusive, a NaN difference not offered.
+ * W > 0 is false for W <= 0 and for a NaN W: such a point is offered nothing
+ * whatever the window, the infinite one included, and gets match = -1 and
+ * zeros (surfhip_homography_batch likewise counts w <= 0 as an outlier).  So
+ * a matrix that holds a NaN, or is all zero, makes its pair match nothing,
+ * deterministically.  Forward, back direction and SURFHIP_MATCH_MUTUAL
+ * clearing are those of surfhip_match_batch_window over this "offered"; only
+ * the five match fields of set-1 points below n1 are written.
+ *   With the identity matrix and finite coordinates the result is, bit for
+ *   bit, that of surfhip_match_batch_window with the same window and flags.
+ *   With the infinite window as well it is that of surfhip_match_batch /
+ *   surfhip_match_batch_cross, for points with W > 0.
+ * The tile skipping works on the boxes of the predicted positions and, as in
+ * the window call, changes no bit of the result.  Asynchronous on `stream`,
+ * no host synchronisation, no allocation.  SURFHIP_ERR_INVALID for everything
+ * surfhip_match_batch_window rejects and for an h_stride that is neither 0
+ * nor >= 9 -- these for npairs == 0 too -- and for a NULL or misaligned d_h
+ * or d_scratch with npairs > 0; otherwise npairs == 0 returns SURFHIP_OK
+ * without touching the GPU. */
+size_t surfhip_match_batch_guided_scratch(int npairs, int slots1, int slots2, int flags);
+int surfhip_match_batch_guided(surfhip_point* d_pts1, const float* d_desc1, const int* d_counts1, int slots1,
+                               const surfhip_point* d_pts2, const float* d_desc2, const int* d_counts2, int slots2,
+                               int npairs, int nfeatures, int flags,
+                               const float* d_h, int h_stride,
+                               const surfhip_match_window* window, void* d_scratch, void* stream);
 
 /* ---------------------------------------------------------- homography --
  * Batched RANSAC homographies (no reference counterpart: main.cpp:250-262

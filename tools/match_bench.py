@@ -30,6 +30,21 @@ downloaded points: the factor the kernel can at best reach.  --cross does the
 same against surfhip_match_batch_cross (SURFHIP_MATCH_MUTUAL).
 
     python tools/match_bench.py --window 32 [--cross] [--reps 7] [--inner 4]
+
+--guided R times surfhip_match_batch_guided on the same detected frames, all
+calls alternating in one run.  (1) The 255 consecutive pairs:
+surfhip_match_batch_window with +-R px against the guided call with +-R px and
+the identity matrix (h_stride 0); the two must write the same bytes (exit
+status 1 if not).  (2) A moving camera: set 2 is each frame's own keypoints
+mapped through a known similarity (roll 3 degrees, zoom 1.02, pan (120, -40) px
+about the frame centre; fp64, rounded to fp32, re-sorted by row and column
+inside every (octave, level) group, descriptors travelling with their points):
+the guided call with +-R px around the prediction under that matrix against the
+window call opened just wide enough to hold every true displacement.  It
+prints times, matches (and how many are the true partner) and the kept (block,
+tile) and (wave, tile) shares of both.  --cross adds SURFHIP_MATCH_MUTUAL.
+
+    python tools/match_bench.py --guided 32 [--cross] [--reps 7] [--inner 4]
 """
 from __future__ import annotations
 
@@ -166,6 +181,12 @@ def kept_tile_shares(surf, pts, counts, win):
     fp32 box tests keep, computed from the downloaded points (flags 0: full
     tiles only).  Random points would keep nearly all; detect_batch's order
     (octave, level, row, column) is what makes the boxes narrow."""
+    return kept_pair_shares(pts[:-1], counts[:-1], pts[1:], counts[1:], win)
+
+
+def kept_pair_shares(pts1, counts1, pts2, counts2, win):
+    """The same for pair i = pts1[i] (its x, y: the positions the window is
+    measured from) against pts2[i]."""
     w = np.asarray(win, np.float32)
     inf = np.float32(np.inf)
 
@@ -180,13 +201,13 @@ def kept_tile_shares(surf, pts, counts, win):
 
     tot = {128: 0, 32: 0}
     kept = {128: 0, 32: 0}
-    for i in range(len(counts) - 1):
-        n1, nscan = int(counts[i]), 32 * (int(counts[i + 1]) // 32)
+    for i in range(len(counts1)):
+        n1, nscan = int(counts1[i]), 32 * (int(counts2[i]) // 32)
         if n1 == 0 or nscan == 0:
             continue
-        b = boxes(pts[i + 1], nscan, 32)
+        b = boxes(pts2[i], nscan, 32)
         for group in (128, 32):
-            a = boxes(pts[i], n1, group)
+            a = boxes(pts1[i], n1, group)
             with np.errstate(invalid="ignore"):
                 keep = (~(b[0][None] - a[1][:, None] > w[1]) & ~(b[1][None] - a[0][:, None] < w[0])
                         & ~(b[2][None] - a[3][:, None] > w[3]) & ~(b[3][None] - a[2][:, None] < w[2]))
@@ -276,6 +297,151 @@ def bench_window(surf, torch, radius, cross, frames_n, reps, inner, width=1920, 
         raise SystemExit("the infinite window disagrees with the unwindowed call")
 
 
+def predict_f32(h, x, y):
+    """surfhip_match_batch_guided's predicted position, its fp32 operations."""
+    h = np.asarray(h, np.float32)
+    with np.errstate(all="ignore"):
+        xx = (h[0] * x + h[1] * y) + h[2]
+        yy = (h[3] * x + h[4] * y) + h[5]
+        ww = (h[6] * x + h[7] * y) + h[8]
+        nan = np.float32(np.nan)
+        return np.where(ww > 0, xx / ww, nan), np.where(ww > 0, yy / ww, nan)
+
+
+def moved_set(pts, counts, h64, height, init_sample=2):
+    """Every frame's own keypoints mapped through the 3 x 3 matrix h64 (fp64,
+    rounded to fp32) and re-sorted as detect_batch would have written them:
+    inside each (octave, level) group by row, then column.  The groups are
+    read off the canonical order of the input: a new one starts where the
+    octave changes or y falls by more than a quarter of the frame height; a
+    row is the octave's sampling step, init_sample << octave, of the new y.
+    Returns (moved points, perm) with moved[i, j] = map(pts[i, perm[i, j]])."""
+    moved = pts.copy()
+    perm = np.tile(np.arange(pts.shape[1]), (len(pts), 1))
+    for i, n in enumerate(counts):
+        p = pts[i, :n]
+        x, y = p["x"].astype(np.float64), p["y"].astype(np.float64)
+        w = h64[2, 0] * x + h64[2, 1] * y + h64[2, 2]
+        mx = ((h64[0, 0] * x + h64[0, 1] * y + h64[0, 2]) / w).astype(np.float32)
+        my = ((h64[1, 0] * x + h64[1, 1] * y + h64[1, 2]) / w).astype(np.float32)
+        start = np.zeros(n, bool)
+        start[1:] = (p["o"][1:] != p["o"][:-1]) | (p["y"][1:] < p["y"][:-1] - 0.25 * height)
+        group = np.cumsum(start)
+        row = np.floor(my / (init_sample * 2.0 ** p["o"])).astype(np.int64)
+        order = np.lexsort((mx, row, group))
+        perm[i, :n] = order
+        moved[i, :n] = p[order]
+        moved["x"][i, :n], moved["y"][i, :n] = mx[order], my[order]
+    return moved, perm
+
+
+def bench_guided(surf, torch, radius, cross, frames_n, reps, inner, width=1920, height=1080, thresh=4.0,
+                 slots=8192):
+    """surfhip_match_batch_guided against surfhip_match_batch_window, all four
+    calls alternating in one run on one detected batch of synthetic frames:
+    the identity on the consecutive pairs (the same bytes, the cost of the
+    guided mode itself), and a moving camera (see the module docstring)."""
+    dev = torch.device("cuda", 0)
+    surf.set_device(0)
+    B, npairs = frames_n, frames_n - 1
+    pitch = surf.align_up(width, 128)
+    d_frames = torch.from_numpy(surf.synth_frames(B, width, height, pitch)).to(dev)
+    param = surf.make_param(4, thresh, False, 9, 2, True, False, 4)
+    nf = param.nfeatures
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    det = surf.Detector(param, width, height, max_batch=B, max_pts=slots, stream=stream)
+    d_pts = torch.zeros(B * slots * 48, dtype=torch.uint8, device=dev)
+    d_desc = torch.empty(B * slots * nf, dtype=torch.float32, device=dev)
+    d_cnt = torch.zeros(B, dtype=torch.int32, device=dev)
+    det.detect_batch(d_frames.data_ptr(), B, pitch, height * pitch, d_pts.data_ptr(), d_desc.data_ptr(),
+                     d_cnt.data_ptr())
+    torch.cuda.synchronize()
+    flags = surf.MATCH_MUTUAL if cross else 0
+    d_scratch = torch.empty(max(surf.match_batch_guided_scratch_bytes(npairs, slots, slots, flags), 16),
+                            dtype=torch.uint8, device=dev)
+    counts = d_cnt.cpu().numpy()
+    pts = d_pts.cpu().numpy().view(surf.POINT_DTYPE).reshape(B, slots).copy()
+
+    # the moving camera: roll 3 degrees, zoom 1.02, pan (120, -40) about the frame centre
+    a, b = 1.02 * np.cos(np.radians(3.0)), 1.02 * np.sin(np.radians(3.0))
+    cx, cy = width / 2.0, height / 2.0
+    h32 = np.array([a, -b, cx - a * cx + b * cy + 120.0, b, a, cy - b * cx - a * cy - 40.0, 0, 0, 1], np.float32)
+    moved, perm = moved_set(pts[:npairs], counts[:npairs], h32.astype(np.float64).reshape(3, 3), height)
+    live = np.arange(slots)[None, :] < counts[:npairs, None]
+    with np.errstate(invalid="ignore"):
+        # the true displacements, as the window call measures them: one fp32 subtraction per axis
+        back = np.argsort(perm, axis=1)                            # set-1 point k lies at set-2 index back[i, k]
+        tx = np.take_along_axis(moved["x"], back, axis=1) - pts[:npairs]["x"]
+        ty = np.take_along_axis(moved["y"], back, axis=1) - pts[:npairs]["y"]
+    wide = (float(tx[live].min()), float(tx[live].max()), float(ty[live].min()), float(ty[live].max()))
+    tight = (-radius, radius, -radius, radius)
+    d_moved = torch.from_numpy(moved.view(np.uint8).reshape(-1)).to(dev)
+    d_perm = torch.from_numpy(perm).to(dev)
+    d_mdesc = torch.take_along_dim(d_desc.view(B, slots, nf)[:npairs], d_perm[:, :, None], dim=1).contiguous()
+    d_h = torch.from_numpy(np.concatenate([np.array([1, 0, 0, 0, 1, 0, 0, 0, 1], np.float32), h32])).to(dev)
+    d_out = torch.zeros(npairs * slots * 48, dtype=torch.uint8, device=dev)      # set 1 of the moving-camera calls
+
+    consecutive = (d_pts.data_ptr(), d_desc.data_ptr(), d_cnt.data_ptr(), slots,
+                   d_pts.data_ptr() + 48 * slots, d_desc.data_ptr() + 4 * slots * nf, d_cnt.data_ptr() + 4, slots)
+    camera = (d_out.data_ptr(), d_desc.data_ptr(), d_cnt.data_ptr(), slots,
+              d_moved.data_ptr(), d_mdesc.data_ptr(), d_cnt.data_ptr(), slots)
+    sp = d_scratch.data_ptr()
+    calls = {
+        "window": lambda: surf.match_batch_window(*consecutive, npairs, nf, flags, tight, sp, stream),
+        "guided_identity": lambda: surf.match_batch_guided(*consecutive, npairs, nf, flags, d_h.data_ptr(), 0, tight,
+                                                           sp, stream),
+        "wide_window": lambda: surf.match_batch_window(*camera, npairs, nf, flags, wide, sp, stream),
+        "guided_camera": lambda: surf.match_batch_guided(*camera, npairs, nf, flags, d_h.data_ptr() + 36, 0, tight,
+                                                         sp, stream),
+    }
+    out = {}
+    for name, fn in calls.items():                  # warm-up, and the results to compare
+        if name in ("wide_window", "guided_camera"):
+            d_out.copy_(d_pts[:npairs * slots * 48])
+        fn()
+        torch.cuda.synchronize()
+        src = d_out if name in ("wide_window", "guided_camera") else d_pts
+        out[name] = src.cpu().numpy().view(surf.POINT_DTYPE).reshape(-1, slots)[:npairs].copy()
+    same = out["window"].tobytes() == out["guided_identity"].tobytes()
+    times = {name: [] for name in calls}
+    for _ in range(reps):                           # the calls alternate inside one run
+        for name, fn in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(inner):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1) / inner)
+    res = {"case": f"{npairs} pairs of {B} {width}x{height} frames, nf={nf} flags={flags}, guided +-{radius} px"
+                   + (", mutual-best" if cross else ""),
+           "reps": reps, "inner": inner, "keypoints_mean": round(float(counts.mean()), 1),
+           "set1_points": int(live.sum()), "identity_bit_identical": same,
+           "camera_matrix": [round(float(v), 6) for v in h32], "wide_window": [round(v, 3) for v in wide]}
+    for name, t in times.items():
+        res[f"{name}_ms"] = round(float(np.median(t)), 4)
+        res[f"{name}_ms_range"] = [round(min(t), 4), round(max(t), 4)]
+    res["guided_identity_over_window"] = round(res["guided_identity_ms"] / res["window_ms"], 4)
+    res["guided_camera_over_wide_window"] = round(res["guided_camera_ms"] / res["wide_window_ms"], 4)
+    res["matches_window"] = int((out["window"]["match"][live] >= 0).sum())
+    pred = pts[:npairs].copy()
+    pred["x"], pred["y"] = predict_f32(h32, pts[:npairs]["x"], pts[:npairs]["y"])
+    for name, p1, win in (("wide_window", pts[:npairs], wide), ("guided_camera", pred, tight)):
+        m = out[name]["match"]
+        res[f"matches_{name}"] = int((m[live] >= 0).sum())
+        res[f"true_partner_{name}"] = int((m[live] == back[live]).sum())
+        block_share, wave_share = kept_pair_shares(p1, counts[:npairs], moved, counts[:npairs], win)
+        res[f"kept_block_tile_share_{name}"] = round(block_share, 4)
+        res[f"kept_wave_tile_share_{name}"] = round(wave_share, 4)
+    block_share, wave_share = kept_tile_shares(surf, pts, counts, tight)
+    res["kept_block_tile_share_window"] = round(block_share, 4)
+    res["kept_wave_tile_share_window"] = round(wave_share, 4)
+    print(json.dumps(res), flush=True)
+    det.close()
+    if not same:
+        raise SystemExit("surfhip_match_batch_guided with the identity disagrees with surfhip_match_batch_window")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=3000)
@@ -288,10 +454,15 @@ def main():
                     help="--batch: time surfhip_match_batch against surfhip_match_batch_cross instead")
     ap.add_argument("--window", type=float, default=0.0, metavar="R",
                     help="time surfhip_match_batch_window with +-R px on detected frames (--cross: with MUTUAL)")
-    ap.add_argument("--frames", type=int, default=256, help="--window: synthetic 1920x1080 frames to detect")
+    ap.add_argument("--guided", type=float, default=0.0, metavar="R",
+                    help="time surfhip_match_batch_guided with +-R px against the window call (--cross: with MUTUAL)")
+    ap.add_argument("--frames", type=int, default=256, help="--window, --guided: synthetic 1920x1080 frames to detect")
     args = ap.parse_args()
     import torch
     surf = load_surf()
+    if args.guided > 0:
+        bench_guided(surf, torch, args.guided, args.cross, args.frames, args.reps, args.inner)
+        return
     if args.window > 0:
         bench_window(surf, torch, args.window, args.cross, args.frames, args.reps, args.inner)
         return
