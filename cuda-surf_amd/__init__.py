@@ -142,6 +142,8 @@ _sigs = {
     "surfhip_match_batch_guided": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "surfhip_homography_batch": (_i, [_vp, _vp, _i, _i, C.c_float, C.c_float, _i, C.c_uint32, _vp, _vp, _vp]),
     "surfhip_homography_lds_capacity": (_i, []),
+    "surfhip_fundamental_batch": (_i, [_vp, _vp, _i, _i, C.c_float, C.c_float, _i, C.c_uint32, _vp, _vp, _vp]),
+    "surfhip_fundamental_lds_capacity": (_i, []),
     "surfhip_ingest_create": (_i, [C.POINTER(_vp), _vp, _i]),
     "surfhip_ingest_destroy": (_i, [_vp]),
     "surfhip_ingest_acquire": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_sz)]),
@@ -718,6 +720,28 @@ def homography_batch(pts1_ptr: int, counts1_ptr: int, slots1: int, npairs: int, 
     bytes or None."""
     check(_lib.surfhip_homography_batch(pts1_ptr, counts1_ptr, slots1, npairs, max_ambiguity, inlier_thresh, nhyp,
                                         seed & 0xFFFFFFFF, out_ptr, inlier_ptr, stream), "surfhip_homography_batch")
+
+
+# ----------------------------------------------------------- fundamental
+
+FUND_OK, FUND_TOO_FEW, FUND_DEGENERATE = 0, 1, 2
+FUNDAMENTAL_DTYPE = np.dtype([("f", "<f4", (9,)), ("status", "<i4"), ("ncand", "<i4"), ("ninliers", "<i4"),
+                              ("rms", "<f4"), ("reserved", "<i4", (3,))])
+assert FUNDAMENTAL_DTYPE.itemsize == 64
+# candidates per pair the kernel keeps in LDS (larger pairs are exact too, only slower)
+FUNDAMENTAL_LDS_CAPACITY = int(_lib.surfhip_fundamental_lds_capacity())
+
+
+def fundamental_batch(pts1_ptr: int, counts1_ptr: int, slots1: int, npairs: int, out_ptr: int,
+                      inlier_ptr: int | None = None, max_ambiguity: float = 0.95, inlier_thresh: float = 3.0,
+                      nhyp: int = 1024, seed: int = 0, stream=None) -> None:
+    """surfhip_fundamental_batch: one RANSAC fundamental matrix ((match_x,
+    match_y, 1) F (x, y, 1)^T = 0) per pair from the match fields match_batch
+    left in the set-1 points ([npairs][slots1], device counts), asynchronous
+    on `stream`.  out_ptr: [npairs] FUNDAMENTAL_DTYPE records; inlier_ptr:
+    [npairs][slots1] bytes or None."""
+    check(_lib.surfhip_fundamental_batch(pts1_ptr, counts1_ptr, slots1, npairs, max_ambiguity, inlier_thresh, nhyp,
+                                         seed & 0xFFFFFFFF, out_ptr, inlier_ptr, stream), "surfhip_fundamental_batch")
 
 
 # ---------------------------------------------------------------- frames

@@ -1290,6 +1290,26 @@ int surfhip_homography_batch(const surfhip_point* pts1, const int* counts1, int 
 
 int surfhip_homography_lds_capacity(void) { return kHomogCap; }
 
+static_assert(sizeof(surfhip_fundamental) == 64, "surfhip_fundamental is 64 bytes");
+static_assert(offsetof(surfhip_fundamental, f) == 0 && offsetof(surfhip_fundamental, status) == 36,
+              "surfhip_fundamental has surfhip_homography's offsets");
+
+int surfhip_fundamental_batch(const surfhip_point* pts1, const int* counts1, int slots1, int npairs,
+                              float max_ambiguity, float inlier_thresh, int nhyp, uint32_t seed,
+                              surfhip_fundamental* out, uint8_t* inlier, void* stream)
+{
+    if (npairs < 0 || slots1 <= 0 || nhyp < 1 || nhyp > 4096 || !std::isfinite(max_ambiguity) ||
+        !(max_ambiguity > 0.0f) || !std::isfinite(inlier_thresh) || !(inlier_thresh > 0.0f))
+        return SURFHIP_ERR_INVALID;
+    if (npairs == 0) return SURFHIP_OK;
+    if (!pts1 || !counts1 || !out) return SURFHIP_ERR_INVALID;
+    HIPCHK(launch_fundamental_batch(pts1, counts1, slots1, npairs, max_ambiguity, inlier_thresh, nhyp, seed, out,
+                                    inlier, (hipStream_t)stream));
+    return SURFHIP_OK;
+}
+
+int surfhip_fundamental_lds_capacity(void) { return kFundCap; }
+
 /* ------------------------------------------------------------- ingest --
  * Pipelined host -> HBM -> result-slab ring.  The
  * reference feeds one frame per call through a blocking cudaMemcpy2D of a

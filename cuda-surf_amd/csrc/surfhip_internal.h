@@ -312,6 +312,12 @@ constexpr int kHomogCap = 3072;
 hipError_t launch_homography_batch(const surfhip_point* pts, const int* counts, int slots, int npairs, float max_amb,
                                    float thresh, int nhyp, uint32_t seed, surfhip_homography* out, uint8_t* inlier,
                                    hipStream_t s);
+// Batched RANSAC fundamental matrices (surfhip_fundamental.hip): the same
+// shape of kernel; kFundCap candidates per pair stay in LDS.
+constexpr int kFundCap = 3072;
+hipError_t launch_fundamental_batch(const surfhip_point* pts, const int* counts, int slots, int npairs, float max_amb,
+                                    float thresh, int nhyp, uint32_t seed, surfhip_fundamental* out, uint8_t* inlier,
+                                    hipStream_t s);
 // bytes ahead of a result slab's points: int32 header[4], then the frames' counts padded to 16 B
 inline size_t slab_head_bytes(int nframes) { return 16 + (((size_t)nframes * 4 + 15) & ~(size_t)15); }
 // (sch.offsets: the prefix of counts, as the batch's launch_sort left it)

@@ -590,6 +590,80 @@ int surfhip_homography_batch(const surfhip_point* d_pts1, const int* d_counts1, 
  * exact, the rest is re-read from the point array. */
 int surfhip_homography_lds_capacity(void);
 
+/* --------------------------------------------------------- fundamental --
+ * Batched RANSAC fundamental matrices (no reference counterpart): one 3 x 3
+ * matrix F with (match_x, match_y, 1) F (x, y, 1)^T = 0 per frame pair, the
+ * model of a stereo rig or of a camera that translates through a scene with
+ * depth, from the match fields surfhip_match_batch left in the set-1
+ * points, asynchronous on `stream`, one launch sequence, no scratch, no host
+ * synchronisation.
+ *   d_pts1    : [npairs][slots1] SurfPoint slots, as surfhip_match_batch
+ *               wrote them; only x, y, match, match_x, match_y and ambiguity
+ *               are read, nothing is written
+ *   d_counts1 : [npairs] int, read on the device, clamped to [0, slots1]
+ *   d_out     : [npairs] results
+ *   d_inlier  : [npairs][slots1] bytes or NULL: 1 for a final inlier, 0 for
+ *               every other slot (slots at or past the count included)
+ * A point below the count is a candidate when match >= 0 and ambiguity <=
+ * max_ambiguity; candidates keep the order of their indices.
+ *
+ * Distance: the squared Sampson distance of (x, y) -> (u, v) = (match_x,
+ * match_y) under f, in fp32, every written operation rounded once:
+ *   a  = (f0*x + f1*y) + f2;   b  = (f3*x + f4*y) + f5;   c = (f6*x + f7*y) + f8;
+ *   a' = (f0*u + f3*v) + f6;   b' = (f1*u + f4*v) + f7;
+ *   r  = (u*a + v*b) + c;      d  = (a*a + b*b) + (a'*a' + b'*b');
+ *   e2 = (r*r) / d;            inlier  <=>  e2 < inlier_thresh^2
+ * (strict; d == 0 or any NaN: outlier).
+ *
+ * Search: nhyp (1 .. 4096) eight-point hypotheses, their samples drawn by a
+ * counter hash of (seed, hypothesis index, ncand) alone, so a
+ * pair gives the same bits wherever it sits in a batch and from run to run.
+ * A hypothesis is the null vector of the 8 x 9 epipolar system of its
+ * Hartley-normalised sample (fp64), de-normalised, scaled to Frobenius norm
+ * 1, stored as fp32; it is not rank-2 projected.  A sample with coincident
+ * points or whose system has no one-dimensional null space (last pivot <=
+ * 1e-7 of the first under full pivoting) scores nothing.  The hypothesis
+ * with the most inliers wins, the lowest index on a tie.
+ *
+ * Refinement: exactly two rounds, the first over the winner's inliers: the
+ * Hartley-normalised 8-point least squares over the current inliers (fp64:
+ * the eigenvector of the smallest eigenvalue of the 9 x 9 normal matrix),
+ * the smallest singular value of that matrix set to 0, de-normalised, scaled
+ * to Frobenius norm 1, the entry of largest magnitude (the lowest index on a
+ * tie) positive, stored as fp32; then a recount over all candidates.  f,
+ * ninliers, rms and the mask belong to the second round's recount under the
+ * f that is returned.
+ *
+ * Fewer than 8 candidates: SURFHIP_FUND_TOO_FEW.  No hypothesis with 8
+ * inliers, a round with fewer than 8 inliers, coincident inliers, a normal
+ * matrix whose second smallest eigenvalue is <= 1e-12 of its largest (the
+ * inliers do not determine F: all on one line, say), a non-finite result or
+ * a vanishing norm: SURFHIP_FUND_DEGENERATE.  Both with f all zero (under
+ * which nothing is an inlier), ninliers = 0, rms = 0 and a zero mask row.
+ * The output never holds a NaN or an infinity.
+ * SURFHIP_ERR_INVALID for npairs < 0, slots1 <= 0, nhyp outside 1 .. 4096,
+ * an inlier_thresh or max_ambiguity that is not finite and positive, or a
+ * NULL d_pts1 / d_counts1 / d_out with npairs > 0; npairs == 0 returns
+ * SURFHIP_OK without touching the GPU. */
+#define SURFHIP_FUND_OK          0
+#define SURFHIP_FUND_TOO_FEW     1   /* fewer than 8 candidates */
+#define SURFHIP_FUND_DEGENERATE  2   /* no usable hypothesis / refit */
+typedef struct surfhip_fundamental {  /* 64 B, same offsets as surfhip_homography */
+    float f[9];        /* row-major; (match_x, match_y, 1) F (x, y, 1)^T = 0; ||f|| = 1, rank 2 when status == OK */
+    int   status;
+    int   ncand;       /* points that passed the filter */
+    int   ninliers;    /* of the final model */
+    float rms;         /* root mean squared Sampson distance of the final inliers, px */
+    int   reserved[3]; /* written as 0 */
+} surfhip_fundamental;
+int surfhip_fundamental_batch(const surfhip_point* d_pts1, const int* d_counts1, int slots1,
+                              int npairs, float max_ambiguity, float inlier_thresh,
+                              int nhyp, uint32_t seed, surfhip_fundamental* d_out,
+                              uint8_t* d_inlier, void* stream);
+/* Candidates per pair the kernel keeps in LDS; pairs with more are still
+ * exact, the rest is re-read from the point array. */
+int surfhip_fundamental_lds_capacity(void);
+
 /* ------------------------------------------------------------- ingest --
  * Pipelined host-frame ingest.  Replaces the
  * per-frame blocking cudaMemcpy2D of a pageable frame (main.cpp:212-226) and
