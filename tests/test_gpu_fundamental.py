@@ -1,6 +1,6 @@
 """GPU tests of surfhip_fundamental_batch (batched RANSAC fundamental matrices
 from the match fields of the set-1 points).  The host reference is numpy
-float64, written here: the Sampson distance, the candidate filter, the
+float64, in ransac_ref.py: the Sampson distance, the candidate filter, the
 sampling hash, the normalised 8-point fit with its rank-2 projection, and a
 restatement of the whole call (the same samples, unprojected hypotheses, two
 refits) that has to recover a planted scene on the CPU before the GPU's
@@ -14,18 +14,15 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from ransac_ref import AMB, AMB_ABOVE, THR, candidate_mask, fit_8pt, restate, sampson
 
 pytestmark = pytest.mark.gpu
 
 FRAME_W, FRAME_H = 1920.0, 1080.0
-THR = 3.0
-AMB = np.float32(0.95)
-AMB_ABOVE = np.nextafter(AMB, np.float32(2))          # the first fp32 that fails `ambiguity <= 0.95f`
 SLOTS = 160
 COUNTS = (0, 1, 7, 8, 9, 31, 64, 65, 96, 159, 160)
 TWO_MODEL_PAIR = 10                                    # 30 % of its candidates follow CAM_SECOND
 OUTLIER_PX = 60.0                                      # outliers: at least this far from their epipolar line
-RANK_TOL = 1e-7                                        # a sample is degenerate below this singular-value ratio
 K = np.array([[1400.0, 0, 960.0], [0, 1400.0, 540.0], [0, 0, 1.0]])
 
 
@@ -57,22 +54,6 @@ def true_f(cam):
     return f / np.linalg.norm(f)
 
 
-def sampson(f, x, y, u, v):
-    """Signed Sampson distance of (x, y) -> (u, v) under row-major f, px:
-    r / sqrt(d) of the header's formula, in float64; d == 0 is infinitely far."""
-    f = np.asarray(f, np.float64).reshape(3, 3)
-    x, y, u, v = (np.asarray(a, np.float64) for a in (x, y, u, v))
-    a = f[0, 0] * x + f[0, 1] * y + f[0, 2]
-    b = f[1, 0] * x + f[1, 1] * y + f[1, 2]
-    c = f[2, 0] * x + f[2, 1] * y + f[2, 2]
-    a2 = f[0, 0] * u + f[1, 0] * v + f[2, 0]
-    b2 = f[0, 1] * u + f[1, 1] * v + f[2, 1]
-    r = u * a + v * b + c
-    d = a * a + b * b + a2 * a2 + b2 * b2
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return np.where(d > 0, r / np.sqrt(d), np.inf)
-
-
 def line_distance(f, x, y, u, v):
     """Distance of (u, v) from the epipolar line of (x, y), px."""
     f = np.asarray(f, np.float64).reshape(3, 3)
@@ -80,118 +61,6 @@ def line_distance(f, x, y, u, v):
     b = f[1, 0] * x + f[1, 1] * y + f[1, 2]
     c = f[2, 0] * x + f[2, 1] * y + f[2, 2]
     return np.abs(u * a + v * b + c) / np.hypot(a, b)
-
-
-def hartley(x, y):
-    cx, cy = x.mean(), y.mean()
-    s = np.sqrt(2) / np.hypot(x - cx, y - cy).mean()
-    return (x - cx) * s, (y - cy) * s, np.array([[s, 0, -s * cx], [0, s, -s * cy], [0, 0, 1]])
-
-
-def epipolar_rows(xn, yn, un, vn):
-    return np.stack([un * xn, un * yn, un, vn * xn, vn * yn, vn, xn, yn, np.ones_like(xn)], -1)
-
-
-def unit_signed(f):
-    """Frobenius norm 1; the entry of largest magnitude (the first on a tie) positive."""
-    f = f.reshape(9) / np.linalg.norm(f)
-    return f if f[np.argmax(np.abs(f))] > 0 else -f
-
-
-def fit_8pt(x, y, u, v):
-    """The documented cost in float64, by SVD of the system itself instead of
-    Jacobi on its normal matrix: Hartley-normalise both point sets, the right
-    singular vector of the smallest singular value of the n x 9 epipolar
-    system, the smallest singular value of that 3 x 3 matrix set to 0,
-    de-normalise, Frobenius norm 1, sign."""
-    x, y, u, v = (np.asarray(a, np.float64) for a in (x, y, u, v))
-    assert len(x) >= 8
-    xn, yn, t1 = hartley(x, y)
-    un, vn, t2 = hartley(u, v)
-    fn = np.linalg.svd(epipolar_rows(xn, yn, un, vn))[2][-1].reshape(3, 3)
-    uu, s, vt = np.linalg.svd(fn)
-    fn = uu @ np.diag([s[0], s[1], 0.0]) @ vt
-    return unit_signed(t2.T @ fn @ t1)
-
-
-def fmix32(x):
-    x &= 0xFFFFFFFF
-    x ^= x >> 16
-    x = (x * 0x85EBCA6B) & 0xFFFFFFFF
-    x ^= x >> 13
-    x = (x * 0xC2B2AE35) & 0xFFFFFFFF
-    x ^= x >> 16
-    return x
-
-
-def sample8(seed, hyp, n):
-    """Hypothesis hyp's 8 distinct candidate ranks below n: draw j picks the
-    d(j)-th, in ascending order, of the n - j ranks not taken yet."""
-    taken, idx = [], []
-    for j in range(8):
-        r = fmix32(seed ^ ((0x9E3779B9 * (8 * hyp + j + 1)) & 0xFFFFFFFF))
-        d = r % (n - j)
-        for s in sorted(taken):
-            if d >= s:
-                d += 1
-        taken.append(d)
-        idx.append(d)
-    return idx
-
-
-def hypotheses(x, y, u, v, nhyp, seed):
-    """[nhyp][9] unprojected 8-point hypotheses (zero where the sample is
-    degenerate), in float64."""
-    n = len(x)
-    idx = np.array([sample8(seed, h, n) for h in range(nhyp)])
-    out = np.zeros((nhyp, 9))
-    for h in range(nhyp):
-        i = idx[h]
-        if not (np.hypot(x[i] - x[i].mean(), y[i] - y[i].mean()).mean() > 0 and
-                np.hypot(u[i] - u[i].mean(), v[i] - v[i].mean()).mean() > 0):
-            continue
-        xn, yn, t1 = hartley(x[i], y[i])
-        un, vn, t2 = hartley(u[i], v[i])
-        _, s, vt = np.linalg.svd(epipolar_rows(xn, yn, un, vn))
-        if not s[7] > RANK_TOL * s[0]:
-            continue
-        f = t2.T @ vt[-1].reshape(3, 3) @ t1
-        out[h] = (f / np.linalg.norm(f)).reshape(9)
-    return out
-
-
-def candidate_mask(pts, count, amb=AMB):
-    n = min(max(int(count), 0), len(pts))
-    ok = (pts["match"] >= 0) & (pts["ambiguity"] <= np.float32(amb))
-    ok[n:] = False
-    return ok
-
-
-def restate(pts, count, thr=THR, amb=AMB, nhyp=256, seed=0):
-    """The whole call in float64: (status, f[9] as fp32, mask over the slots);
-    status 0 OK, 1 TOO_FEW, 2 DEGENERATE."""
-    cand = np.nonzero(candidate_mask(pts, count, amb))[0]
-    zero = (np.zeros(9, np.float32), np.zeros(len(pts), bool))
-    if len(cand) < 8:
-        return (1,) + zero
-    x, y, u, v = (pts[k][cand].astype(np.float64) for k in ("x", "y", "match_x", "match_y"))
-    hyp = hypotheses(x, y, u, v, nhyp, seed).astype(np.float32)
-    counts = np.array([(np.abs(sampson(h, x, y, u, v)) < thr).sum() if h.any() else 0 for h in hyp])
-    best = int(np.argmax(counts))                      # the first of the largest
-    if counts[best] < 8:
-        return (2,) + zero
-    f = hyp[best]
-    for _ in range(2):
-        inl = np.abs(sampson(f, x, y, u, v)) < thr
-        if inl.sum() < 8:
-            return (2,) + zero
-        f = fit_8pt(x[inl], y[inl], u[inl], v[inl]).astype(np.float32)
-    inl = np.abs(sampson(f, x, y, u, v)) < thr
-    if inl.sum() < 8:
-        return (2,) + zero
-    mask = np.zeros(len(pts), bool)
-    mask[cand[inl]] = True
-    return 0, f, mask
 
 
 def restatement_recovers(pts, count, planted, thr=THR, nhyp=256, seed=0):

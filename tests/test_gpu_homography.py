@@ -1,6 +1,6 @@
 """GPU tests of surfhip_homography_batch (batched RANSAC homographies from
 the match fields of the set-1 points).  The host reference is numpy float64,
-written here: the transfer error, the candidate filter and the documented
+in ransac_ref.py: the transfer error, the candidate filter and the documented
 least-squares cost (inhomogeneous Hartley-normalised DLT)."""
 from __future__ import annotations
 
@@ -11,13 +11,11 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from ransac_ref import AMB, AMB_ABOVE, THR, candidate_mask, fit_dlt, project, transfer_err
 
 pytestmark = pytest.mark.gpu
 
 FRAME_W, FRAME_H = 1920.0, 1080.0
-THR = 3.0
-AMB = np.float32(0.95)
-AMB_ABOVE = np.nextafter(AMB, np.float32(2))          # the first fp32 that fails `ambiguity <= 0.95f`
 SLOTS = 160
 COUNTS = (0, 1, 3, 4, 5, 31, 32, 33, 64, 65, 159, 160)
 TWO_MODEL_PAIR = 11                                    # 30 % of its candidates follow H1
@@ -35,57 +33,11 @@ H2 = np.array([[1.05, -0.08, -70.0], [0.08, 1.05, 90.0], [-3.0e-5, 4.0e-5, 1.0]]
 
 # ------------------------------------------------------- float64 reference
 
-def project(h, x, y):
-    h = np.asarray(h, np.float64).reshape(3, 3)
-    x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
-    w = h[2, 0] * x + h[2, 1] * y + h[2, 2]
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return (h[0, 0] * x + h[0, 1] * y + h[0, 2]) / w, (h[1, 0] * x + h[1, 1] * y + h[1, 2]) / w, w
-
-
-def transfer_err(h, x, y, u, v):
-    """One-way transfer error in image 2, px; w <= 0 is infinitely far."""
-    px, py, w = project(h, x, y)
-    e = np.hypot(px - np.asarray(u, np.float64), py - np.asarray(v, np.float64))
-    return np.where(w > 0, e, np.inf)
-
-
-def fit_dlt(x, y, u, v):
-    """The documented cost, in float64 by QR/SVD least squares instead of
-    normal equations: Hartley-normalise both point sets (centroid to the
-    origin, mean distance sqrt 2), minimise sum (x h1 + y h2 + h3 - u (x h7 +
-    y h8) - u)^2 + (x h4 + y h5 + h6 - v (x h7 + y h8) - v)^2 with h9 = 1,
-    de-normalise, scale to h33 = 1."""
-    x, y, u, v = (np.asarray(a, np.float64) for a in (x, y, u, v))
-    c1, c2 = np.array([x.mean(), y.mean()]), np.array([u.mean(), v.mean()])
-    s1 = np.sqrt(2) / np.hypot(x - c1[0], y - c1[1]).mean()
-    s2 = np.sqrt(2) / np.hypot(u - c2[0], v - c2[1]).mean()
-    xn, yn, un, vn = (x - c1[0]) * s1, (y - c1[1]) * s1, (u - c2[0]) * s2, (v - c2[1]) * s2
-    n, z, o = len(x), np.zeros(len(x)), np.ones(len(x))
-    a = np.concatenate([np.stack([xn, yn, o, z, z, z, -un * xn, -un * yn], 1),
-                        np.stack([z, z, z, xn, yn, o, -vn * xn, -vn * yn], 1)])
-    b = np.concatenate([un, vn])
-    sol = np.linalg.lstsq(a, b, rcond=None)[0]
-    hn = np.append(sol, 1.0).reshape(3, 3)
-    t1 = np.array([[s1, 0, -s1 * c1[0]], [0, s1, -s1 * c1[1]], [0, 0, 1]])
-    t2i = np.array([[1 / s2, 0, c2[0]], [0, 1 / s2, c2[1]], [0, 0, 1]])
-    h = t2i @ hn @ t1
-    assert n >= 4
-    return h / h[2, 2]
-
-
 def corner_displacement(ha, hb):
     cx, cy = np.array([0, FRAME_W, FRAME_W, 0]), np.array([0, 0, FRAME_H, FRAME_H])
     ax, ay, _ = project(ha, cx, cy)
     bx, by, _ = project(hb, cx, cy)
     return float(np.hypot(ax - bx, ay - by).max())
-
-
-def candidate_mask(pts, count, amb=AMB):
-    n = min(max(int(count), 0), len(pts))
-    ok = (pts["match"] >= 0) & (pts["ambiguity"] <= np.float32(amb))
-    ok[n:] = False
-    return ok
 
 
 def band_recheck(pts, count, res, mask, thr=THR, amb=AMB):
