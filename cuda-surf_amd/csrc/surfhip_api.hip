@@ -1274,21 +1274,30 @@ int surfhip_match_batch_guided(surfhip_point* pts1, const float* f1, const int* 
 static_assert(sizeof(surfhip_homography) == 64, "surfhip_homography is 64 bytes");
 static_assert(offsetof(surfhip_homography, h) == 0, "surfhip_match_batch_guided reads h at the record's start");
 
-int surfhip_homography_batch(const surfhip_point* pts1, const int* counts1, int slots1, int npairs,
-                             float max_ambiguity, float inlier_thresh, int nhyp, uint32_t seed,
-                             surfhip_homography* out, uint8_t* inlier, void* stream)
+// the arguments surfhip_homography_batch and surfhip_fundamental_batch share; the scalars first, so
+// that they are checked for npairs == 0 too
+static int ransac_args(const void* pts1, const int* counts1, int slots1, int npairs, float max_ambiguity,
+                       float inlier_thresh, int nhyp, const void* out)
 {
     if (npairs < 0 || slots1 <= 0 || nhyp < 1 || nhyp > 4096 || !std::isfinite(max_ambiguity) ||
         !(max_ambiguity > 0.0f) || !std::isfinite(inlier_thresh) || !(inlier_thresh > 0.0f))
         return SURFHIP_ERR_INVALID;
-    if (npairs == 0) return SURFHIP_OK;
-    if (!pts1 || !counts1 || !out) return SURFHIP_ERR_INVALID;
+    if (npairs > 0 && (!pts1 || !counts1 || !out)) return SURFHIP_ERR_INVALID;
+    return SURFHIP_OK;
+}
+
+int surfhip_homography_batch(const surfhip_point* pts1, const int* counts1, int slots1, int npairs,
+                             float max_ambiguity, float inlier_thresh, int nhyp, uint32_t seed,
+                             surfhip_homography* out, uint8_t* inlier, void* stream)
+{
+    const int bad = ransac_args(pts1, counts1, slots1, npairs, max_ambiguity, inlier_thresh, nhyp, out);
+    if (bad != SURFHIP_OK || npairs == 0) return bad;
     HIPCHK(launch_homography_batch(pts1, counts1, slots1, npairs, max_ambiguity, inlier_thresh, nhyp, seed, out,
                                    inlier, (hipStream_t)stream));
     return SURFHIP_OK;
 }
 
-int surfhip_homography_lds_capacity(void) { return kHomogCap; }
+int surfhip_homography_lds_capacity(void) { return kRansacCap; }
 
 static_assert(sizeof(surfhip_fundamental) == 64, "surfhip_fundamental is 64 bytes");
 static_assert(offsetof(surfhip_fundamental, f) == 0 && offsetof(surfhip_fundamental, status) == 36,
@@ -1298,17 +1307,14 @@ int surfhip_fundamental_batch(const surfhip_point* pts1, const int* counts1, int
                               float max_ambiguity, float inlier_thresh, int nhyp, uint32_t seed,
                               surfhip_fundamental* out, uint8_t* inlier, void* stream)
 {
-    if (npairs < 0 || slots1 <= 0 || nhyp < 1 || nhyp > 4096 || !std::isfinite(max_ambiguity) ||
-        !(max_ambiguity > 0.0f) || !std::isfinite(inlier_thresh) || !(inlier_thresh > 0.0f))
-        return SURFHIP_ERR_INVALID;
-    if (npairs == 0) return SURFHIP_OK;
-    if (!pts1 || !counts1 || !out) return SURFHIP_ERR_INVALID;
+    const int bad = ransac_args(pts1, counts1, slots1, npairs, max_ambiguity, inlier_thresh, nhyp, out);
+    if (bad != SURFHIP_OK || npairs == 0) return bad;
     HIPCHK(launch_fundamental_batch(pts1, counts1, slots1, npairs, max_ambiguity, inlier_thresh, nhyp, seed, out,
                                     inlier, (hipStream_t)stream));
     return SURFHIP_OK;
 }
 
-int surfhip_fundamental_lds_capacity(void) { return kFundCap; }
+int surfhip_fundamental_lds_capacity(void) { return kRansacCap; }
 
 /* ------------------------------------------------------------- ingest --
  * Pipelined host -> HBM -> result-slab ring.  The

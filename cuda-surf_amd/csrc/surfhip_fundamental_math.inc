@@ -1,10 +1,14 @@
 // surfhip_fundamental_math.inc -- the per-thread arithmetic of
 // surfhip_fundamental.hip (included there, inside its anonymous namespace):
-// the Sampson distance, the 8-point sampler, the 8-point solver of one
-// hypothesis and the tail of a refit (9 x 9 and 3 x 3 cyclic Jacobi, rank-2
-// projection, de-normalisation).  Nothing here touches threadIdx or LDS by
+// the Sampson distance, the 8-point solver of one hypothesis and the tail of
+// a refit (9 x 9 and 3 x 3 cyclic Jacobi, rank-2 projection,
+// de-normalisation).  Nothing here touches threadIdx or LDS by
 // name; the functions are __host__ __device__ so that a host program can run
-// the very same arithmetic against a float64 reference.
+// the very same arithmetic against a float64 reference.  The sampler of the
+// hypotheses, which the homography kernel shares, is pulled in from its own
+// file, so that this one include still gives a host program all of it.
+
+#include "surfhip_ransac_sample.inc"
 
 constexpr double kFdRankTol = 1e-7;         // a sample is degenerate when |last pivot| <= this * |first pivot|
 constexpr double kFdEigTol = 1e-12;         // a refit is degenerate when its second smallest eigenvalue <= this * the largest
@@ -25,43 +29,6 @@ __host__ __device__ __forceinline__ float fd_sampson2(const float* f, float x, f
     const float r = (u * a + v * b) + c;
     const float d = (a * a + b * b) + (a2 * a2 + b2 * b2);
     return (r * r) / d;
-}
-
-__host__ __device__ __forceinline__ uint32_t fd_fmix32(uint32_t x)
-{
-    x ^= x >> 16; x *= 0x85EBCA6Bu;
-    x ^= x >> 13; x *= 0xC2B2AE35u;
-    x ^= x >> 16;
-    return x;
-}
-
-// K distinct indices below n (n >= K): draw j picks among the n - j indices
-// not taken yet, in ascending order of those
-template <int K>
-__host__ __device__ __forceinline__ void fd_sample(uint32_t seed, uint32_t hyp, int n, int (&idx)[K])
-{
-    int s[K];                               // the picks so far, ascending
-#pragma unroll
-    for (int i = 0; i < K; ++i) s[i] = 0;
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        const uint32_t r = fd_fmix32(seed ^ (0x9E3779B9u * ((uint32_t)K * hyp + (uint32_t)j + 1u)));
-        int d = (int)(r % (uint32_t)(n - j));
-#pragma unroll
-        for (int i = 0; i < K; ++i)
-            if (i < j && d >= s[i]) ++d;
-        idx[j] = d;
-        int cur = d;
-#pragma unroll
-        for (int i = 0; i < K; ++i) {
-            if (i < j) {
-                const int lo = min(s[i], cur), hi = max(s[i], cur);
-                s[i] = lo;
-                cur = hi;
-            }
-            if (i == j) s[i] = cur;
-        }
-    }
 }
 
 __host__ __device__ __forceinline__ void fd_cswap(bool c, double& a, double& b)

@@ -305,16 +305,14 @@ hipError_t launch_match_batch_guided(surfhip_point* pts1, const float* f1, const
                                      const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
                                      int npairs, int nf, int flags, const float* hm, int h_stride,
                                      const surfhip_match_window& win, void* scratch, hipStream_t s);
-// Batched RANSAC homographies (surfhip_homography.hip): one workgroup per
-// pair on the match fields of its set-1 points; kHomogCap candidates per
-// pair stay in LDS, more are re-read from the point array.
-constexpr int kHomogCap = 3072;
+// Batched RANSAC homographies and fundamental matrices (surfhip_ransac.inc,
+// with the model of surfhip_homography.hip or surfhip_fundamental.hip): one
+// workgroup per pair on the match fields of its set-1 points; kRansacCap
+// candidates per pair stay in LDS, more are re-read from the point array.
+constexpr int kRansacCap = 3072;
 hipError_t launch_homography_batch(const surfhip_point* pts, const int* counts, int slots, int npairs, float max_amb,
                                    float thresh, int nhyp, uint32_t seed, surfhip_homography* out, uint8_t* inlier,
                                    hipStream_t s);
-// Batched RANSAC fundamental matrices (surfhip_fundamental.hip): the same
-// shape of kernel; kFundCap candidates per pair stay in LDS.
-constexpr int kFundCap = 3072;
 hipError_t launch_fundamental_batch(const surfhip_point* pts, const int* counts, int slots, int npairs, float max_amb,
                                     float thresh, int nhyp, uint32_t seed, surfhip_fundamental* out, uint8_t* inlier,
                                     hipStream_t s);

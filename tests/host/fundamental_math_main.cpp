@@ -1,16 +1,17 @@
 // fundamental_math_main.cpp -- runs the __host__ __device__ functions of
-// surfhip_fundamental_math.inc on the CPU, for tests/test_fundamental_math_host.py.
+// surfhip_fundamental_math.inc and surfhip_ransac_sample.inc on the CPU, for
+// tests/test_fundamental_math_host.py.
 //
 //   fundamental_math_main <cases> <results>
 //
 // Both files are streams of little-endian records.  A case starts with an
 // int32 opcode and an int32 count of items:
-//   1 sample8     per item uint32 seed, uint32 hyp, int32 n      -> 8 int32
+//   1 sample      per item uint32 seed, uint32 hyp, int32 n, int32 K (4 or 8) -> K int32
 //   2 sampson2    per item 13 float32 (f[9], x, y, u, v)         -> 1 float32
 //   3 eight_point per item 32 float64 (x[8], y[8], u[8], v[8])   -> int32 ok, 9 float32
 //   4 jacobi      per item int32 n, n*n float64 (row-major A)    -> n*n float64 A, n*n float64 V
 //   5 refit_solve per item 42 float64 (m[36], cx, cy, s1, cu, cv, s2) -> int32 ok, 9 float32
-//   6 sample8 histogram: uint32 seed, int32 n, int32 nhyp (count = 1)
+//   6 sample histogram: uint32 seed, int32 n, int32 nhyp, int32 K (4 or 8) (count = 1)
 //                 -> n int64 hits per index, int32 bad (samples with a repeated or out-of-range index)
 // Exit status 0 when every case was read and written.
 #include <algorithm>
@@ -27,6 +28,7 @@ using std::min;
 
 namespace {
 #include "surfhip_fundamental_math.inc"
+#include "surfhip_ransac_sample.inc"
 
 template <class T>
 bool get(FILE* f, T* p, size_t n = 1)
@@ -40,18 +42,46 @@ bool put(FILE* f, const T* p, size_t n = 1)
     return fwrite(p, sizeof(T), n, f) == n;
 }
 
+template <int K>
+bool sample_item(uint32_t seed, uint32_t hyp, int32_t n, FILE* out)
+{
+    if (n < K) return false;
+    int idx[K];
+    fd_sample<K>(seed, hyp, n, idx);
+    int32_t o[K];
+    for (int j = 0; j < K; ++j) o[j] = idx[j];
+    return put(out, o, K);
+}
+
+template <int K>
+bool sample_histogram(uint32_t seed, int32_t n, int32_t nhyp, FILE* out)
+{
+    if (n < K) return false;
+    std::vector<int64_t> hits((size_t)n, 0);
+    int32_t bad = 0;
+    for (int32_t h = 0; h < nhyp; ++h) {
+        int idx[K];
+        fd_sample<K>(seed, (uint32_t)h, n, idx);
+        bool ok = true;
+        for (int j = 0; j < K; ++j) {
+            ok = ok && idx[j] >= 0 && idx[j] < n;
+            for (int i = 0; i < j; ++i) ok = ok && idx[i] != idx[j];
+        }
+        if (!ok) { ++bad; continue; }
+        for (int j = 0; j < K; ++j) ++hits[(size_t)idx[j]];
+    }
+    return put(out, hits.data(), hits.size()) && put(out, &bad);
+}
+
 bool run_case(int op, int count, FILE* in, FILE* out)
 {
     for (int it = 0; it < count; ++it) {
         if (op == 1) {
             uint32_t sh[2];
-            int32_t n;
-            if (!get(in, sh, 2) || !get(in, &n) || n < 8) return false;
-            int idx[8];
-            fd_sample<8>(sh[0], sh[1], n, idx);
-            int32_t o[8];
-            for (int j = 0; j < 8; ++j) o[j] = idx[j];
-            if (!put(out, o, 8)) return false;
+            int32_t nk[2];
+            if (!get(in, sh, 2) || !get(in, nk, 2) || (nk[1] != 4 && nk[1] != 8)) return false;
+            if (!(nk[1] == 4 ? sample_item<4>(sh[0], sh[1], nk[0], out) : sample_item<8>(sh[0], sh[1], nk[0], out)))
+                return false;
         } else if (op == 2) {
             float a[13];
             if (!get(in, a, 13)) return false;
@@ -78,22 +108,10 @@ bool run_case(int op, int count, FILE* in, FILE* out)
             if (!put(out, &ok) || !put(out, f, 9)) return false;
         } else if (op == 6) {
             uint32_t seed;
-            int32_t n, nhyp;
-            if (!get(in, &seed) || !get(in, &n) || !get(in, &nhyp) || n < 8) return false;
-            std::vector<int64_t> hits((size_t)n, 0);
-            int32_t bad = 0;
-            for (int32_t h = 0; h < nhyp; ++h) {
-                int idx[8];
-                fd_sample<8>(seed, (uint32_t)h, n, idx);
-                bool ok = true;
-                for (int j = 0; j < 8; ++j) {
-                    ok = ok && idx[j] >= 0 && idx[j] < n;
-                    for (int i = 0; i < j; ++i) ok = ok && idx[i] != idx[j];
-                }
-                if (!ok) { ++bad; continue; }
-                for (int j = 0; j < 8; ++j) ++hits[(size_t)idx[j]];
-            }
-            if (!put(out, hits.data(), hits.size()) || !put(out, &bad)) return false;
+            int32_t a[3];                               // n, nhyp, K
+            if (!get(in, &seed) || !get(in, a, 3) || (a[2] != 4 && a[2] != 8)) return false;
+            if (!(a[2] == 4 ? sample_histogram<4>(seed, a[0], a[1], out) : sample_histogram<8>(seed, a[0], a[1], out)))
+                return false;
         } else {
             return false;
         }

@@ -1,5 +1,6 @@
-"""surfhip_fundamental_math.inc on the CPU: tests/host/fundamental_math_main.cpp
-includes the very file the kernel includes, built here with g++ and the
+"""surfhip_fundamental_math.inc and the sampler of both RANSAC kernels,
+surfhip_ransac_sample.inc, on the CPU: tests/host/fundamental_math_main.cpp
+includes the very files the kernels include, built here with g++ and the
 address and undefined-behaviour sanitizers, and each of its functions is
 compared with a float64 numpy reference (ransac_ref.py, numpy.linalg).  No
 GPU is involved.  The bounds are derived in the tests that use them; the
@@ -101,38 +102,40 @@ def sine(a, b):
 # ----------------------------------------------------------------- sampler
 
 SAMPLE_SEEDS = (0, 3, 0x80000000, 0xFFFFFFFF)
-SAMPLE_N = tuple(range(8, 41)) + (255, 256, 257, 3071, 3072, 3073, 65535, 1 << 20)
+SAMPLE_TAIL = (255, 256, 257, 3071, 3072, 3073, 65535, 1 << 20)
 
 
 def test_sample_is_the_documented_draw(prog, tmp_path):
-    items = [(s, h, n) for n in SAMPLE_N for s in SAMPLE_SEEDS for h in range(64)]
-    cases = head(1, len(items)) + b"".join(struct.pack("<IIi", *it) for it in items)
-    got = np.frombuffer(run(prog, tmp_path, cases), np.int32).reshape(len(items), 8)
-    want = np.array([sample(8, s, h, n) for s, h, n in items])
-    assert (got == want).all(), items[int(np.nonzero((got != want).any(1))[0][0])]
+    for K in (4, 8):
+        items = [(s, h, n) for n in tuple(range(K, 41)) + SAMPLE_TAIL for s in SAMPLE_SEEDS for h in range(64)]
+        cases = head(1, len(items)) + b"".join(struct.pack("<IIii", *it, K) for it in items)
+        got = np.frombuffer(run(prog, tmp_path, cases), np.int32).reshape(len(items), K)
+        want = np.array([sample(K, s, h, n) for s, h, n in items])
+        assert (got == want).all(), (K, items[int(np.nonzero((got != want).any(1))[0][0])])
     assert sample(8, 0, 3, 160) == [52, 44, 61, 71, 17, 45, 57, 132]
 
 
 def test_sample_is_distinct_and_uniform(prog, tmp_path):
-    """Over N = 20,000 hypotheses an index of n lies in a sample with
-    probability p = 8 / n, so its hits are binomial(N, p): within 5 sigma =
-    5 sqrt(N p (1 - p)) of N p (for n = 8 that is exactly N)."""
+    """Over N = 20,000 hypotheses an index of n lies in a sample of K with
+    probability p = K / n, so its hits are binomial(N, p): within 5 sigma =
+    5 sqrt(N p (1 - p)) of N p (for n = K that is exactly N)."""
     nhyp = 20000
-    for seed in (0, 0xFFFFFFFF):
-        ns = range(8, 13)
-        cases = b"".join(head(6, 1) + struct.pack("<Iii", seed, n, nhyp) for n in ns)
-        out, at = run(prog, tmp_path, cases), 0
-        for n in ns:
-            hits = np.frombuffer(out, np.int64, n, at)
-            bad = struct.unpack_from("<i", out, at + 8 * n)[0]
-            at += 8 * n + 4
-            p = 8.0 / n
-            dev = np.abs(hits - nhyp * p).max()
-            print(f"fd_sample<8> n {n} seed {seed:#x}: largest deviation {dev:.0f} hits, "
-                  f"5 sigma {5 * np.sqrt(nhyp * p * (1 - p)):.0f}")
-            assert bad == 0 and hits.sum() == 8 * nhyp
-            assert dev <= 5 * np.sqrt(nhyp * p * (1 - p))
-        assert at == len(out)
+    for K in (4, 8):
+        for seed in (0, 0xFFFFFFFF):
+            ns = range(K, K + 5)
+            cases = b"".join(head(6, 1) + struct.pack("<Iiii", seed, n, nhyp, K) for n in ns)
+            out, at = run(prog, tmp_path, cases), 0
+            for n in ns:
+                hits = np.frombuffer(out, np.int64, n, at)
+                bad = struct.unpack_from("<i", out, at + 8 * n)[0]
+                at += 8 * n + 4
+                p = float(K) / n
+                dev = np.abs(hits - nhyp * p).max()
+                print(f"fd_sample<{K}> n {n} seed {seed:#x}: largest deviation {dev:.0f} hits, "
+                      f"5 sigma {5 * np.sqrt(nhyp * p * (1 - p)):.0f}")
+                assert bad == 0 and hits.sum() == K * nhyp
+                assert dev <= 5 * np.sqrt(nhyp * p * (1 - p))
+            assert at == len(out)
 
 
 # ----------------------------------------------------------------- sampson
