@@ -1186,45 +1186,65 @@ int surfhip_match(surfhip_point* pts1, const surfhip_point* pts2, const float* f
     return SURFHIP_OK;
 }
 
+// the checks the four batched match calls share; the scalars first, so that they are checked for npairs == 0 too.
+// b: the sets, npairs, nf and flags as the caller gave them (MATCH_GUIDED: hm, h_stride too); allowed: the call's
+// flag bits; window: required unless MATCH_PLAIN, and copied into b; scratch: checked where the call needs one
+static int match_batch_args(MatchBatch& b, int allowed, int mode, const surfhip_match_window* window,
+                            bool need_scratch, const void* scratch)
+{
+    if (b.npairs < 0 || b.slots1 <= 0 || b.slots2 <= 0 || b.nf < 4 || b.nf > 1024 || (b.nf & 3) ||
+        (b.flags & ~allowed))
+        return SURFHIP_ERR_INVALID;
+    if (mode != MATCH_PLAIN) {
+        // (a NaN bound fails its comparison)
+        if (!window || !(window->dx_min <= window->dx_max) || !(window->dy_min <= window->dy_max))
+            return SURFHIP_ERR_INVALID;
+        b.win = *window;
+    }
+    if (mode == MATCH_GUIDED && b.h_stride != 0 && b.h_stride < 9) return SURFHIP_ERR_INVALID;
+    if (b.npairs == 0) return SURFHIP_OK;
+    if (!b.pts1 || !b.f1 || !b.counts1 || !b.pts2 || !b.f2 || !b.counts2) return SURFHIP_ERR_INVALID;
+    if (need_scratch && (!scratch || ((uintptr_t)scratch & 15))) return SURFHIP_ERR_INVALID;
+    if (mode == MATCH_GUIDED && (!b.hm || ((uintptr_t)b.hm & 3))) return SURFHIP_ERR_INVALID;
+    return SURFHIP_OK;
+}
+
+constexpr int kMatchBatchFlags = SURFHIP_MATCH_FULL_TAIL | SURFHIP_MATCH_SAME_LAPLACE;
+
 int surfhip_match_batch(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
                         const surfhip_point* pts2, const float* f2, const int* counts2, int slots2, int npairs,
                         int nf, int flags, void* stream)
 {
-    if (npairs < 0 || slots1 <= 0 || slots2 <= 0 || nf < 4 || nf > 1024 || (nf & 3) ||
-        (flags & ~(SURFHIP_MATCH_FULL_TAIL | SURFHIP_MATCH_SAME_LAPLACE)))
-        return SURFHIP_ERR_INVALID;
-    if (npairs == 0) return SURFHIP_OK;
-    if (!pts1 || !f1 || !counts1 || !pts2 || !f2 || !counts2) return SURFHIP_ERR_INVALID;
-    HIPCHK(launch_match_batch(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf, flags,
-                              (hipStream_t)stream));
+    MatchBatch b = {pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf, flags};
+    const int bad = match_batch_args(b, kMatchBatchFlags, MATCH_PLAIN, nullptr, false, nullptr);
+    if (bad != SURFHIP_OK || npairs == 0) return bad;
+    HIPCHK(launch_match_batch(b, MATCH_PLAIN, nullptr, (hipStream_t)stream));
     return SURFHIP_OK;
 }
 
 size_t surfhip_match_batch_cross_scratch(int npairs, int slots1, int slots2)
 {
     if (npairs <= 0 || slots1 <= 0 || slots2 <= 0) return 0;
-    return match_batch_cross_scratch_bytes(npairs, slots2);
+    return match_batch_scratch_bytes(MATCH_PLAIN, npairs, slots2, SURFHIP_MATCH_MUTUAL);
 }
 
+// (SURFHIP_MATCH_MUTUAL is not one of this call's flags: it is what the call means)
 int surfhip_match_batch_cross(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
                               const surfhip_point* pts2, const float* f2, const int* counts2, int slots2, int npairs,
                               int nf, int flags, void* scratch, void* stream)
 {
-    if (npairs < 0 || slots1 <= 0 || slots2 <= 0 || nf < 4 || nf > 1024 || (nf & 3) ||
-        (flags & ~(SURFHIP_MATCH_FULL_TAIL | SURFHIP_MATCH_SAME_LAPLACE)))
-        return SURFHIP_ERR_INVALID;
-    if (npairs == 0) return SURFHIP_OK;
-    if (!pts1 || !f1 || !counts1 || !pts2 || !f2 || !counts2 || !scratch || ((uintptr_t)scratch & 15))
-        return SURFHIP_ERR_INVALID;
-    HIPCHK(launch_match_batch_cross(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf, flags, scratch,
-                                    (hipStream_t)stream));
+    MatchBatch b = {pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf, flags};
+    const int bad = match_batch_args(b, kMatchBatchFlags, MATCH_PLAIN, nullptr, true, scratch);
+    if (bad != SURFHIP_OK || npairs == 0) return bad;
+    b.flags |= SURFHIP_MATCH_MUTUAL;
+    HIPCHK(launch_match_batch(b, MATCH_PLAIN, scratch, (hipStream_t)stream));
     return SURFHIP_OK;
 }
 
 size_t surfhip_match_batch_window_scratch(int npairs, int slots1, int slots2, int flags)
 {
     if (npairs <= 0 || slots1 <= 0 || slots2 <= 0) return 0;
-    return match_batch_window_scratch_bytes(npairs, slots2, flags);
+    return match_batch_scratch_bytes(MATCH_WINDOW, npairs, slots2, flags);
 }
 
 int surfhip_match_batch_window(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
@@ -1232,17 +1252,10 @@ int surfhip_match_batch_window(surfhip_point* pts1, const float* f1, const int* 
                                int npairs, int nf, int flags, const surfhip_match_window* window, void* scratch,
                                void* stream)
 {
-    if (npairs < 0 || slots1 <= 0 || slots2 <= 0 || nf < 4 || nf > 1024 || (nf & 3) ||
-        (flags & ~(SURFHIP_MATCH_FULL_TAIL | SURFHIP_MATCH_SAME_LAPLACE | SURFHIP_MATCH_MUTUAL)))
-        return SURFHIP_ERR_INVALID;
-    // (a NaN bound fails its comparison)
-    if (!window || !(window->dx_min <= window->dx_max) || !(window->dy_min <= window->dy_max))
-        return SURFHIP_ERR_INVALID;
-    if (npairs == 0) return SURFHIP_OK;
-    if (!pts1 || !f1 || !counts1 || !pts2 || !f2 || !counts2 || !scratch || ((uintptr_t)scratch & 15))
-        return SURFHIP_ERR_INVALID;
-    HIPCHK(launch_match_batch_window(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf, flags, *window,
-                                     scratch, (hipStream_t)stream));
+    MatchBatch b = {pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf, flags};
+    const int bad = match_batch_args(b, kMatchBatchFlags | SURFHIP_MATCH_MUTUAL, MATCH_WINDOW, window, true, scratch);
+    if (bad != SURFHIP_OK || npairs == 0) return bad;
+    HIPCHK(launch_match_batch(b, MATCH_WINDOW, scratch, (hipStream_t)stream));
     return SURFHIP_OK;
 }
 
@@ -1256,18 +1269,12 @@ int surfhip_match_batch_guided(surfhip_point* pts1, const float* f1, const int* 
                                int npairs, int nf, int flags, const float* h, int h_stride,
                                const surfhip_match_window* window, void* scratch, void* stream)
 {
-    if (npairs < 0 || slots1 <= 0 || slots2 <= 0 || nf < 4 || nf > 1024 || (nf & 3) ||
-        (flags & ~(SURFHIP_MATCH_FULL_TAIL | SURFHIP_MATCH_SAME_LAPLACE | SURFHIP_MATCH_MUTUAL)))
-        return SURFHIP_ERR_INVALID;
-    if (!window || !(window->dx_min <= window->dx_max) || !(window->dy_min <= window->dy_max))
-        return SURFHIP_ERR_INVALID;
-    if (h_stride != 0 && h_stride < 9) return SURFHIP_ERR_INVALID;
-    if (npairs == 0) return SURFHIP_OK;
-    if (!pts1 || !f1 || !counts1 || !pts2 || !f2 || !counts2 || !scratch || ((uintptr_t)scratch & 15) || !h ||
-        ((uintptr_t)h & 3))
-        return SURFHIP_ERR_INVALID;
-    HIPCHK(launch_match_batch_guided(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf, flags, h,
-                                     h_stride, *window, scratch, (hipStream_t)stream));
+    MatchBatch b = {pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf, flags};
+    b.hm = h;
+    b.h_stride = h_stride;
+    const int bad = match_batch_args(b, kMatchBatchFlags | SURFHIP_MATCH_MUTUAL, MATCH_GUIDED, window, true, scratch);
+    if (bad != SURFHIP_OK || npairs == 0) return bad;
+    HIPCHK(launch_match_batch(b, MATCH_GUIDED, scratch, (hipStream_t)stream));
     return SURFHIP_OK;
 }
 

@@ -277,34 +277,56 @@ size_t match_scratch_bytes(int n1, int n2, int flags);
 hipError_t launch_match(surfhip_point* pts1, const surfhip_point* pts2, const float* f1, const float* f2, int n1,
                         int n2, int nf, int flags, void* scratch, hipStream_t s);
 // Batched matching on the f32 MFMA: pair i = frame i of set 1 ([npairs][slots1]
-// points / descriptors, counts on the device) against frame i of set 2; no
-// scratch.  The point arrays may overlap (set 2 = set 1 advanced one frame).
-hipError_t launch_match_batch(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
-                              const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
-                              int npairs, int nf, int flags, hipStream_t s);
-// The same with the mutual-best filter: a match (p1 -> p2) stays only when p1
-// is the best set-1 point of p2.  scratch: match_batch_cross_scratch_bytes()
-// of device memory in any state (one 64-bit word per set-2 slot, cleared on s).
-size_t match_batch_cross_scratch_bytes(int npairs, int slots2);
-hipError_t launch_match_batch_cross(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
-                                    const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
-                                    int npairs, int nf, int flags, void* scratch, hipStream_t s);
-// Batched matching inside a search window (flags may carry
-// SURFHIP_MATCH_MUTUAL: then with the mutual-best filter).  scratch:
-// match_batch_window_scratch_bytes() of device memory in any state (16 B per
-// 32 set-2 slots for the tile boxes, then the mutual test's keys).
-size_t match_batch_window_scratch_bytes(int npairs, int slots2, int flags);
-hipError_t launch_match_batch_window(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
-                                     const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
-                                     int npairs, int nf, int flags, const surfhip_match_window& win, void* scratch,
-                                     hipStream_t s);
-// The same with the window measured from each set-1 point's predicted
-// position under its pair's 3 x 3 matrix: the nine row-major floats at
-// hm + i * h_stride in device memory, read in stream order.  Scratch as above.
-hipError_t launch_match_batch_guided(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
-                                     const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
-                                     int npairs, int nf, int flags, const float* hm, int h_stride,
-                                     const surfhip_match_window& win, void* scratch, hipStream_t s);
+// points / descriptors, counts on the device) against frame i of set 2.  The
+// point arrays may overlap (set 2 = set 1 advanced one frame).
+// What is offered to a set-1 point: every set-2 point, those in a window
+// around it, or those in a window around its predicted position.
+enum { MATCH_PLAIN = 0, MATCH_WINDOW = 1, MATCH_GUIDED = 2 };
+// The arguments of a batched match, the kernels' too (by value).  The caller
+// fills the sets, npairs, nf, flags and, by mode, win (MATCH_WINDOW,
+// MATCH_GUIDED) and hm, h_stride (MATCH_GUIDED: pair i's 3 x 3 matrix is the
+// nine row-major floats at hm + i * h_stride in device memory, read in stream
+// order); launch_match_batch places back, boxes and tiles in its scratch.
+struct MatchBatch {
+    surfhip_point* pts1;
+    const float* f1;
+    const int* counts1;
+    int slots1;
+    const surfhip_point* pts2;
+    const float* f2;
+    const int* counts2;
+    int slots2;
+    int npairs, nf, flags;
+    unsigned long long* back;       // SURFHIP_MATCH_MUTUAL: [npairs][slots2] keys of the back direction
+    float4* boxes;                  // not MATCH_PLAIN: [npairs][tiles] boxes of set 2's 32-point tiles
+    int tiles;
+    surfhip_match_window win;
+    const float* hm;
+    int h_stride;
+    // the pairs from p0 on
+    MatchBatch from(int p0) const
+    {
+        MatchBatch b = *this;
+        b.pts1 += (size_t)p0 * slots1;
+        b.f1 += (size_t)p0 * slots1 * nf;
+        b.counts1 += p0;
+        b.pts2 += (size_t)p0 * slots2;
+        b.f2 += (size_t)p0 * slots2 * nf;
+        b.counts2 += p0;
+        b.npairs -= p0;
+        if (back) b.back += (size_t)p0 * slots2;
+        if (boxes) b.boxes += (size_t)p0 * tiles;
+        if (hm) b.hm += (size_t)p0 * h_stride;
+        return b;
+    }
+};
+// flags may carry SURFHIP_MATCH_MUTUAL in every mode: then a match (p1 -> p2)
+// stays only when p1 is the best set-1 point of p2.  scratch:
+// match_batch_scratch_bytes() of device memory in any state, 16-B aligned:
+// first the tile boxes (not MATCH_PLAIN: 16 B per 32 set-2 slots), then the
+// keys (SURFHIP_MATCH_MUTUAL: one 64-bit word per set-2 slot, cleared on s).
+size_t match_batch_scratch_bytes(int mode, int npairs, int slots2, int flags);
+hipError_t launch_match_batch(const MatchBatch& b, int mode, void* scratch, hipStream_t s);
 // Batched RANSAC homographies and fundamental matrices (surfhip_ransac.inc,
 // with the model of surfhip_homography.hip or surfhip_fundamental.hip): one
 // workgroup per pair on the match fields of its set-1 points; kRansacCap

@@ -86,6 +86,13 @@ namespace {
 constexpr int kMatchThreads = 256;
 constexpr int kTilesPerChunk = 2;   // 64 set-2 points per chunk (2 waves / SIMD at 3k x 3k)
 
+// The set-2 points a match scans: the full 32-point tiles of n2 (surfd.cu:2569),
+// or all of them.
+__host__ __device__ __forceinline__ int scanned(int n2, int flags)
+{
+    return (flags & SURFHIP_MATCH_FULL_TAIL) ? n2 : 32 * (n2 / 32);
+}
+
 // Sequential (max, second, index) update with strict '>' (surfd.cu:2611-2620),
 // branch-free (selects, no divergent control flow around the state).
 __device__ __forceinline__ void scan_update(float s, int p2, float& mx, float& sc, int& ix)
@@ -97,23 +104,61 @@ __device__ __forceinline__ void scan_update(float s, int p2, float& mx, float& s
     ix = gt ? p2 : ix;
 }
 
+// The reference's row merge (surfd.cu:2638-2655) and the write of the five
+// match fields.  (M, S, I): row 0's state, which starts the merge; row(r, rm,
+// ri) gives (max, index) of row r = 1 .. 7, in order -- the rows' second scores
+// are not used, equal indices are skipped.  write: this lane writes pts1[p1].
+template <class Row>
+__device__ __forceinline__ void merge_rows_write(surfhip_point* pts1, const surfhip_point* pts2, int p1, bool write,
+                                                 float M, float S, int I, Row row)
+{
+#pragma unroll
+    for (int r = 1; r < 8; ++r) {
+        float rm;
+        int ri;
+        row(r, rm, ri);
+        if (I != ri) {
+            if (rm > M) {
+                S = fmaxf(M, S);
+                M = rm;
+                I = ri;
+            } else if (rm > S) {
+                S = rm;
+            }
+        }
+    }
+    if (!write) return;
+    surfhip_point& q = pts1[p1];
+    q.score = M;
+    q.match = I;
+    q.match_x = I >= 0 ? pts2[I].x : 0.0f;
+    q.match_y = I >= 0 ? pts2[I].y : 0.0f;
+    q.ambiguity = S / (M + 1e-6f);
+}
+
+// NF 64 / 128: the lane's descriptor in VGPRs, unrolled chains.  NF 0: any
+// descriptor length nf (a multiple of 4, <= 1024), runtime trip count.
 template <int NF>
 __global__ __launch_bounds__(kMatchThreads) void k_match_part(const float* __restrict__ f1,
                                                               const float* __restrict__ f2, int n1, int nscan,
                                                               int ntile, float* __restrict__ pmx,
-                                                              float* __restrict__ psc, int* __restrict__ pix)
+                                                              float* __restrict__ psc, int* __restrict__ pix, int nf)
 {
     const int p1 = blockIdx.x * kMatchThreads + threadIdx.x;
     const int q1 = p1 < n1 ? p1 : n1 - 1;
-    float a[NF];
-    const float4* ap = reinterpret_cast<const float4*>(f1 + (size_t)q1 * NF);
+    const int len = NF ? NF : nf;
+    const float* ar = f1 + (size_t)q1 * len;
+    float a[NF ? NF : 1];
+    if constexpr (NF != 0) {
+        const float4* ap = reinterpret_cast<const float4*>(ar);
 #pragma unroll
-    for (int d = 0; d < NF / 4; ++d) {
-        const float4 v = ap[d];
-        a[4 * d] = v.x;
-        a[4 * d + 1] = v.y;
-        a[4 * d + 2] = v.z;
-        a[4 * d + 3] = v.w;
+        for (int d = 0; d < NF / 4; ++d) {
+            const float4 v = ap[d];
+            a[4 * d] = v.x;
+            a[4 * d + 1] = v.y;
+            a[4 * d + 2] = v.z;
+            a[4 * d + 3] = v.w;
+        }
     }
     float mx[8], sc[8];
     int ix[8];
@@ -130,52 +175,14 @@ __global__ __launch_bounds__(kMatchThreads) void k_match_part(const float* __res
         for (int j = 0; j < 32; ++j) {
             const int p2 = 32 * t + j;
             if (p2 < nscan) {
-                const float* b = f2 + (size_t)p2 * NF;
+                const float* b = f2 + (size_t)p2 * len;
                 float s = 0.0f;
+                if constexpr (NF != 0) {
 #pragma unroll
-                for (int d = 0; d < NF; ++d) s = __builtin_fmaf(a[d], b[d], s);
-                scan_update(s, p2, mx[j >> 2], sc[j >> 2], ix[j >> 2]);
-            }
-        }
-    }
-    if (p1 < n1) {
-#pragma unroll
-        for (int g = 0; g < 8; ++g) {
-            const size_t o = ((size_t)blockIdx.y * n1 + p1) * 8 + g;
-            pmx[o] = mx[g];
-            psc[o] = sc[g];
-            pix[o] = ix[g];
-        }
-    }
-}
-
-// Any descriptor length (a multiple of 4, <= 1024): runtime trip count.
-__global__ __launch_bounds__(kMatchThreads) void k_match_part_any(const float* __restrict__ f1,
-                                                                  const float* __restrict__ f2, int n1, int nf,
-                                                                  int nscan, int ntile, float* __restrict__ pmx,
-                                                                  float* __restrict__ psc, int* __restrict__ pix)
-{
-    const int p1 = blockIdx.x * kMatchThreads + threadIdx.x;
-    const int q1 = p1 < n1 ? p1 : n1 - 1;
-    const float* a = f1 + (size_t)q1 * nf;
-    float mx[8], sc[8];
-    int ix[8];
-#pragma unroll
-    for (int g = 0; g < 8; ++g) {
-        mx[g] = 0.0f;
-        sc[g] = 0.0f;
-        ix[g] = -1;
-    }
-    const int t0 = blockIdx.y * kTilesPerChunk;
-    const int t1 = min(t0 + kTilesPerChunk, ntile);
-    for (int t = t0; t < t1; ++t) {
-#pragma unroll
-        for (int j = 0; j < 32; ++j) {
-            const int p2 = 32 * t + j;
-            if (p2 < nscan) {
-                const float* b = f2 + (size_t)p2 * nf;
-                float s = 0.0f;
-                for (int d = 0; d < nf; ++d) s = __builtin_fmaf(a[d], b[d], s);
+                    for (int d = 0; d < NF; ++d) s = __builtin_fmaf(a[d], b[d], s);
+                } else {
+                    for (int d = 0; d < nf; ++d) s = __builtin_fmaf(ar[d], b[d], s);
+                }
                 scan_update(s, p2, mx[j >> 2], sc[j >> 2], ix[j >> 2]);
             }
         }
@@ -217,31 +224,10 @@ __global__ __launch_bounds__(256) void k_match_merge(surfhip_point* __restrict__
             ix = gt ? bi : ix;
         }
     }
-    // Row merge (surfd.cu:2638-2655): row 0 starts the state, the rows'
-    // second scores are not used, equal indices are skipped.
-    float M = mx, S = sc;
-    int I = ix;
-#pragma unroll
-    for (int r = 1; r < 8; ++r) {
-        const float rm = __shfl(mx, (threadIdx.x & ~7) + r);
-        const int ri = __shfl(ix, (threadIdx.x & ~7) + r);
-        if (I != ri) {
-            if (rm > M) {
-                S = fmaxf(M, S);
-                M = rm;
-                I = ri;
-            } else if (rm > S) {
-                S = rm;
-            }
-        }
-    }
-    if (!live || g != 0) return;
-    surfhip_point& q = pts1[p1];
-    q.score = M;
-    q.match = I;
-    q.match_x = I >= 0 ? pts2[I].x : 0.0f;
-    q.match_y = I >= 0 ? pts2[I].y : 0.0f;
-    q.ambiguity = S / (M + 1e-6f);
+    merge_rows_write(pts1, pts2, p1, live && g == 0, mx, sc, ix, [&](int r, float& rm, int& ri) {
+        rm = __shfl(mx, (threadIdx.x & ~7) + r);
+        ri = __shfl(ix, (threadIdx.x & ~7) + r);
+    });
 }
 
 // ---- batched matching on the f32 MFMA ----------------------------------
@@ -253,22 +239,7 @@ constexpr int kBatchPts = 32 * kBatchWaves;         // set-1 points per block
 
 __device__ __forceinline__ int clamp_count(int c, int slots) { return c < 0 ? 0 : (c > slots ? slots : c); }
 
-// One 32 x 32 score tile D[p2][p1] into the lane's four row states: register
-// 4 q + r holds tile position 8 q + 4 h + r, i.e. thread row 2 q + h, r
-// ascending.  lap2: the laplace of tile position (lane & 31), LAP only.
-// CROSS: ks[4 q + r] also gets the score's bits where the pair (p1, p2) counts
-// for the back direction (p2 offered, p1 live, score > 0 -- never a NaN), 0
-// elsewhere; positive floats order like their bits.
-// WIN (surfhip_match_batch_window): the pair also has to lie in the search
-// window w around the lane's point (x1, y1).  WIN_LDS: xy2 holds the tile's
-// 32 x then 32 y (16-B aligned), a lane reads its four positions of a q at
-// once; WIN_SHFL: x2, y2 are those of tile position (lane & 31).  A NaN
-// difference fails every comparison: not offered.
 enum { WIN_OFF = 0, WIN_LDS = 1, WIN_SHFL = 2 };
-
-// What a batch kernel offers: everything, a window around (x1, y1), or a
-// window around the prediction H (x1, y1).
-enum { MATCH_PLAIN = 0, MATCH_WINDOW = 1, MATCH_GUIDED = 2 };
 
 // The predicted position of (x, y) under the row-major 3 x 3 matrix m, in the
 // operation order of transfer_err2 (surfhip_homography.hip), one fp32
@@ -284,12 +255,25 @@ __device__ __forceinline__ void guided_predict(const float* __restrict__ m, floa
     v = front ? Y / W : __builtin_nanf("");
 }
 
-template <bool LAP, bool CROSS = false, int WIN = WIN_OFF>
+// One 32 x 32 score tile D[p2][p1] into the lane's four row states: register
+// 4 q + r holds tile position 8 q + 4 h + r, i.e. thread row 2 q + h, r
+// ascending.  lap2: the laplace of tile position (lane & 31), LAP only.
+// CROSS: ks[4 q + r] also gets the score's bits where the pair (p1, p2) counts
+// for the back direction (p2 offered, p1 live, score > 0 -- never a NaN), 0
+// elsewhere; positive floats order like their bits.
+// WIN (surfhip_match_batch_window): the pair also has to lie in the search
+// window w around the lane's point (x1, y1).  WIN_LDS: xy2 holds the tile's
+// 32 x then 32 y (16-B aligned), a lane reads its four positions of a q at
+// once; WIN_SHFL: x2, y2 are those of tile position (lane & 31).  A NaN
+// difference fails every comparison: not offered.
+// (The kernels call it through scan_lane_tile, which has these in two structs:
+// with the structs read in here, or with cross_reduce behind the same call,
+// the CROSS kernels' registers are allocated differently.)
+template <bool LAP, bool CROSS, int WIN>
 __device__ __forceinline__ void scan_tile(const f32x16& acc, int t, int h, int nscan, int lap1, int lap2,
-                                          float (&mx)[4], float (&sc)[4], int (&ix)[4], bool live1 = false,
-                                          uint32_t* ks = nullptr, const surfhip_match_window* w = nullptr,
-                                          float x1 = 0.0f, float y1 = 0.0f, const float* xy2 = nullptr,
-                                          float x2 = 0.0f, float y2 = 0.0f)
+                                          float (&mx)[4], float (&sc)[4], int (&ix)[4], bool live1, uint32_t* ks,
+                                          const surfhip_match_window* w, float x1, float y1, const float* xy2,
+                                          float x2, float y2)
 {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -358,7 +342,7 @@ __device__ __forceinline__ void cross_fold(uint32_t (&ks)[16], uint32_t (&ki)[16
     }
 }
 
-// The 32 column maxima of a wave's 32 x 32 tile: ks as scan_tile<CROSS> left
+// The 32 column maxima of a wave's 32 x 32 tile: ks as scan_tile's CROSS left
 // it.  Returns, on the lanes with (lane & 31) < 16, the key of tile position
 // j (also returned) over the wave's 32 set-1 points: lane (h, c) ends with
 // register c of half h, position 8 (c >> 2) + 4 h + (c & 3).
@@ -378,6 +362,30 @@ __device__ __forceinline__ u64 cross_reduce(uint32_t (&ks)[16], int p1, int h, i
     return (key >> 32) ? key : 0;
 }
 
+// scan_tile's arguments by name.  The set-1 side, the same for every tile of a
+// lane: h, lap1 (LAP), live1 (CROSS), and w, x1, y1 (WIN).
+struct ScanLane {
+    int h, lap1;
+    bool live1;
+    float x1, y1;
+    const surfhip_match_window* w;
+};
+
+// The set-2 side: tile t, lap2 (LAP), xy2 (WIN_LDS), x2 and y2 (WIN_SHFL).
+struct ScanTile {
+    int t, lap2;
+    const float* xy2 = nullptr;
+    float x2 = 0.0f, y2 = 0.0f;
+};
+
+template <bool LAP, bool CROSS, int WIN>
+__device__ __forceinline__ void scan_lane_tile(const f32x16& acc, int nscan, const ScanLane& me, const ScanTile& tl,
+                                               float (&mx)[4], float (&sc)[4], int (&ix)[4], uint32_t* ks)
+{
+    scan_tile<LAP, CROSS, WIN>(acc, tl.t, me.h, nscan, me.lap1, tl.lap2, mx, sc, ix, me.live1, ks, me.w, me.x1, me.y1,
+                               tl.xy2, tl.x2, tl.y2);
+}
+
 // Lanes l and l ^ 32 hold rows (0, 2, 4, 6) and (1, 3, 5, 7) of point p1;
 // the h = 0 lane merges them as k_match_merge does and writes the point.
 __device__ __forceinline__ void batch_finish(surfhip_point* pts1, const surfhip_point* pts2, int p1, int n1, int h,
@@ -391,28 +399,10 @@ __device__ __forceinline__ void batch_finish(surfhip_point* pts1, const surfhip_
         oix[q] = __shfl_xor(ix[q], 32);
     }
     if (h != 0 || p1 >= n1) return;
-    float M = mx[0], S = sc[0];
-    int I = ix[0];
-#pragma unroll
-    for (int r = 1; r < 8; ++r) {
-        const float rm = (r & 1) ? omx[r >> 1] : mx[r >> 1];
-        const int ri = (r & 1) ? oix[r >> 1] : ix[r >> 1];
-        if (I != ri) {
-            if (rm > M) {
-                S = fmaxf(M, S);
-                M = rm;
-                I = ri;
-            } else if (rm > S) {
-                S = rm;
-            }
-        }
-    }
-    surfhip_point& q = pts1[p1];
-    q.score = M;
-    q.match = I;
-    q.match_x = I >= 0 ? pts2[I].x : 0.0f;
-    q.match_y = I >= 0 ? pts2[I].y : 0.0f;
-    q.ambiguity = S / (M + 1e-6f);
+    merge_rows_write(pts1, pts2, p1, true, mx[0], sc[0], ix[0], [&](int r, float& rm, int& ri) {
+        rm = (r & 1) ? omx[r >> 1] : mx[r >> 1];
+        ri = (r & 1) ? oix[r >> 1] : ix[r >> 1];
+    });
 }
 
 // ---- windowed matching: boxes --------------------------------------------
@@ -456,19 +446,19 @@ __device__ __forceinline__ bool box_may_offer(const float4& a, const float4& b, 
 
 // boxes[pair][tiles]: the box of every scanned 32-point tile of set 2 (the
 // tiles at or past ntile are not written and not read).
-__global__ __launch_bounds__(256) void k_match_tile_boxes(const surfhip_point* pts2, const int* __restrict__ counts2,
-                                                          int slots2, int full_tail, int tiles,
-                                                          float4* __restrict__ boxes)
+__global__ __launch_bounds__(256) void k_match_tile_boxes(const MatchBatch mb)
 {
+    const int* __restrict__ counts2 = mb.counts2;
+    float4* __restrict__ boxes = mb.boxes;
     const int pair = blockIdx.y;
-    const int n2 = clamp_count(counts2[pair], slots2);
-    const int nscan = full_tail ? n2 : 32 * (n2 / 32);
+    const int n2 = clamp_count(counts2[pair], mb.slots2);
+    const int nscan = scanned(n2, mb.flags);
     const int t = blockIdx.x * 8 + (threadIdx.x >> 5);
     const int p2 = 32 * t + (threadIdx.x & 31);
     const bool live = p2 < nscan;
-    const surfhip_point* q = pts2 + (size_t)pair * slots2 + (live ? p2 : 0);
+    const surfhip_point* q = mb.pts2 + (size_t)pair * mb.slots2 + (live ? p2 : 0);
     const float4 b = box_of_32(q->x, q->y, live);
-    if ((threadIdx.x & 31) == 0 && 32 * t < nscan) boxes[(size_t)pair * tiles + t] = b;
+    if ((threadIdx.x & 31) == 0 && 32 * t < nscan) boxes[(size_t)pair * mb.tiles + t] = b;
 }
 
 // pts1 / pts2 may overlap (consecutive frames of one batch): no __restrict__
@@ -487,18 +477,10 @@ __global__ __launch_bounds__(256) void k_match_tile_boxes(const surfhip_point* p
 // GUIDED (surfhip_match_batch_guided): WIN around the lane's prediction under
 // the pair's matrix, the nine floats at hm + pair * h_stride.
 template <int NF, bool LAP, bool CROSS, int MODE = MATCH_PLAIN>
-__global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pts1, const float* __restrict__ f1,
-                                                               const int* __restrict__ counts1, int slots1,
-                                                               const surfhip_point* pts2,
-                                                               const float* __restrict__ f2,
-                                                               const int* __restrict__ counts2, int slots2,
-                                                               int full_tail, u64* __restrict__ back,
-                                                               const float4* __restrict__ boxes, int tiles,
-                                                               surfhip_match_window win,
-                                                               const float* __restrict__ hm, int h_stride)
+__global__ __launch_bounds__(kBatchThreads) void k_match_batch(const MatchBatch mb)
 {
     constexpr bool WIN = MODE != MATCH_PLAIN;
-    constexpr int RS = NF + 4;                              // LDS row: NF / 2 even, NF / 2 odd elements, pad
+    constexpr int RS = NF + 4;                             // LDS row: NF / 2 even, NF / 2 odd elements, pad
     constexpr int C4 = NF / 4;                              // float4 per descriptor
     constexpr int NV = 32 * C4 / kBatchThreads;             // float4 per thread per tile
     static_assert(32 * C4 % kBatchThreads == 0, "tile staging");
@@ -512,7 +494,9 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pt
     __shared__ int tlist[WIN ? kWinChunk : 1];
     __shared__ float4 tbox[WIN ? kWinChunk : 1];
 
-    const int pair = blockIdx.y;
+    const int pair = blockIdx.y, slots1 = mb.slots1, slots2 = mb.slots2;
+    const int* __restrict__ counts1 = mb.counts1;
+    const int* __restrict__ counts2 = mb.counts2;
     const int n1 = clamp_count(counts1[pair], slots1);
     // WIN: workgroups go to the 8 XCDs round-robin by their linear index, and
     // with an even grid.x the blocks that keep most tiles (the small, tall
@@ -522,13 +506,14 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pt
     const int base = bx * kBatchPts;
     if (base >= n1) return;
     const int n2 = clamp_count(counts2[pair], slots2);
-    const int nscan = full_tail ? n2 : 32 * (n2 / 32);
+    const int nscan = scanned(n2, mb.flags);
     const int ntile = (nscan + 31) / 32;
-    pts1 += (size_t)pair * slots1;
-    pts2 += (size_t)pair * slots2;
-    f1 += (size_t)pair * slots1 * NF;
-    f2 += (size_t)pair * slots2 * NF;
-    if constexpr (CROSS) back += (size_t)pair * slots2;
+    surfhip_point* pts1 = mb.pts1 + (size_t)pair * slots1;
+    const surfhip_point* pts2 = mb.pts2 + (size_t)pair * slots2;
+    const float* __restrict__ f1 = mb.f1 + (size_t)pair * slots1 * NF;
+    const float* __restrict__ f2 = mb.f2 + (size_t)pair * slots2 * NF;
+    u64* __restrict__ back = CROSS ? mb.back + (size_t)pair * slots2 : nullptr;
+    const surfhip_match_window& win = mb.win;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int h = lane >> 5, c = lane & 31;
@@ -622,6 +607,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pt
     }
 
     if constexpr (!WIN) {
+        const ScanLane me = {h, lap1, p1 < n1, 0.0f, 0.0f, nullptr};
         if (ntile > 0) {
             load_tile(0);
             store_tile(0);
@@ -651,15 +637,13 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pt
                     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b[4 * k + 2], acc, 0, 0, 0);
                     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b[4 * k + 3], acc, 0, 0, 0);
                 }
+                uint32_t ks[16];
+                scan_lane_tile<LAP, CROSS, WIN_OFF>(acc, nscan, me, {t, lap2}, mx, sc, ix, ks);
                 if constexpr (CROSS) {
-                    uint32_t ks[16];
-                    scan_tile<LAP, true>(acc, t, h, nscan, lap1, lap2, mx, sc, ix, p1 < n1, ks);
                     int j;
                     const u64 key = cross_reduce(ks, p1, h, c, j);
                     if (c < 16 && key)
                         __hip_atomic_fetch_max(&colmax[cur][j], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                } else {
-                    scan_tile<LAP>(acc, t, h, nscan, lap1, lap2, mx, sc, ix);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -671,9 +655,10 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pt
             if (wave == 0 && ntile > 0) send_keys(ntile - 1, ntile - 1);
         }
     } else {
-        boxes += (size_t)pair * tiles;
+        const float4* __restrict__ boxes = mb.boxes + (size_t)pair * mb.tiles;
         float x1 = pts1[q1].x, y1 = pts1[q1].y;
-        if constexpr (MODE == MATCH_GUIDED) guided_predict(hm + (size_t)pair * h_stride, x1, y1, x1, y1);
+        if constexpr (MODE == MATCH_GUIDED) guided_predict(mb.hm + (size_t)pair * mb.h_stride, x1, y1, x1, y1);
+        const ScanLane me = {h, lap1, p1 < n1, x1, y1, &win};
         const float4 mybox = box_of_32(x1, y1, p1 < n1);    // the wave's live points (none: a dead wave)
         if (lane == 0) wbox[wave] = mybox;
         __syncthreads();
@@ -726,18 +711,14 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pt
                 // tall, its waves are not
                 if (wlive && __builtin_amdgcn_readfirstlane(box_may_offer(mybox, tbox[i], win))) {
                     const f32x16 acc = score_tile(cur);
+                    uint32_t ks[16];
+                    scan_lane_tile<LAP, CROSS, WIN_LDS>(acc, nscan, me, {t, lap2, xy2[cur]}, mx, sc, ix, ks);
                     if constexpr (CROSS) {
-                        uint32_t ks[16];
-                        scan_tile<LAP, true, WIN_LDS>(acc, t, h, nscan, lap1, lap2, mx, sc, ix, p1 < n1, ks, &win, x1,
-                                                      y1, xy2[cur]);
                         int j;
                         const u64 key = cross_reduce(ks, p1, h, c, j);
                         if (c < 16 && key)
                             __hip_atomic_fetch_max(&colmax[cur][j], key, __ATOMIC_RELAXED,
                                                    __HIP_MEMORY_SCOPE_WORKGROUP);
-                    } else {
-                        scan_tile<LAP, false, WIN_LDS>(acc, t, h, nscan, lap1, lap2, mx, sc, ix, false, nullptr, &win,
-                                                       x1, y1, xy2[cur]);
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -759,32 +740,27 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(surfhip_point* pt
 // WIN: a wave walks all tile boxes and skips the tiles its own box misses.
 // GUIDED: as in k_match_batch.
 template <bool LAP, bool CROSS, int MODE = MATCH_PLAIN>
-__global__ __launch_bounds__(kBatchThreads) void k_match_batch_any(surfhip_point* pts1,
-                                                                   const float* __restrict__ f1,
-                                                                   const int* __restrict__ counts1, int slots1,
-                                                                   const surfhip_point* pts2,
-                                                                   const float* __restrict__ f2,
-                                                                   const int* __restrict__ counts2, int slots2,
-                                                                   int nf, int full_tail, u64* __restrict__ back,
-                                                                   const float4* __restrict__ boxes, int tiles,
-                                                                   surfhip_match_window win,
-                                                                   const float* __restrict__ hm, int h_stride)
+__global__ __launch_bounds__(kBatchThreads) void k_match_batch_any(const MatchBatch mb)
 {
     constexpr bool WIN = MODE != MATCH_PLAIN;
-    const int pair = blockIdx.y;
+    const int pair = blockIdx.y, slots1 = mb.slots1, slots2 = mb.slots2, nf = mb.nf;
+    const int* __restrict__ counts1 = mb.counts1;
+    const int* __restrict__ counts2 = mb.counts2;
     const int n1 = clamp_count(counts1[pair], slots1);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int bx = WIN ? (blockIdx.x + blockIdx.y) % gridDim.x : blockIdx.x;    // (as in k_match_batch)
     const int base = bx * kBatchPts + 32 * wave;
     if (base >= n1) return;
     const int n2 = clamp_count(counts2[pair], slots2);
-    const int nscan = full_tail ? n2 : 32 * (n2 / 32);
+    const int nscan = scanned(n2, mb.flags);
     const int ntile = (nscan + 31) / 32;
-    pts1 += (size_t)pair * slots1;
-    pts2 += (size_t)pair * slots2;
-    f1 += (size_t)pair * slots1 * nf;
-    f2 += (size_t)pair * slots2 * nf;
-    if constexpr (CROSS) back += (size_t)pair * slots2;
+    surfhip_point* pts1 = mb.pts1 + (size_t)pair * slots1;
+    const surfhip_point* pts2 = mb.pts2 + (size_t)pair * slots2;
+    const float* __restrict__ f1 = mb.f1 + (size_t)pair * slots1 * nf;
+    const float* __restrict__ f2 = mb.f2 + (size_t)pair * slots2 * nf;
+    u64* __restrict__ back = CROSS ? mb.back + (size_t)pair * slots2 : nullptr;
+    const float4* __restrict__ boxes = WIN ? mb.boxes + (size_t)pair * mb.tiles : nullptr;
+    const surfhip_match_window& win = mb.win;
     const int h = lane >> 5, c = lane & 31;
     const int p1 = base + c;
     const int q1 = p1 < n1 ? p1 : n1 - 1;
@@ -801,12 +777,12 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch_any(surfhip_point
     float x1 = 0.0f, y1 = 0.0f;
     float4 mybox = {0, 0, 0, 0};
     if constexpr (WIN) {
-        boxes += (size_t)pair * tiles;
         x1 = pts1[q1].x;
         y1 = pts1[q1].y;
-        if constexpr (MODE == MATCH_GUIDED) guided_predict(hm + (size_t)pair * h_stride, x1, y1, x1, y1);
+        if constexpr (MODE == MATCH_GUIDED) guided_predict(mb.hm + (size_t)pair * mb.h_stride, x1, y1, x1, y1);
         mybox = box_of_32(x1, y1, p1 < n1);
     }
+    const ScanLane me = {h, lap1, p1 < n1, x1, y1, &win};
     constexpr int W = WIN ? WIN_SHFL : WIN_OFF;
     for (int t = 0; t < ntile; ++t) {
         if constexpr (WIN) {
@@ -818,17 +794,13 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch_any(surfhip_point
         const float x2 = WIN ? pts2[q2].x : 0.0f, y2 = WIN ? pts2[q2].y : 0.0f;
         f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         for (int d = 0; d < nf; d += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(r2[d], r1[d], acc, 0, 0, 0);
+        uint32_t ks[16];
+        scan_lane_tile<LAP, CROSS, W>(acc, nscan, me, {t, lap2, nullptr, x2, y2}, mx, sc, ix, ks);
         if constexpr (CROSS) {
-            uint32_t ks[16];
-            scan_tile<LAP, true, W>(acc, t, h, nscan, lap1, lap2, mx, sc, ix, p1 < n1, ks, &win, x1, y1, nullptr, x2,
-                                    y2);
             int j;
             const u64 key = cross_reduce(ks, p1, h, c, j);
             if (c < 16 && key)                              // a key: 32 t + j < nscan
                 __hip_atomic_fetch_max(back + 32 * t + j, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            scan_tile<LAP, false, W>(acc, t, h, nscan, lap1, lap2, mx, sc, ix, false, nullptr, &win, x1, y1, nullptr,
-                                     x2, y2);
         }
     }
     batch_finish(pts1, pts2, p1, n1, h, mx, sc, ix);
@@ -837,13 +809,14 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch_any(surfhip_point
 // The mutual-best filter, one thread per set-1 point below n1: a match whose
 // set-2 point has another back best (the key's low word is not ~p1) is
 // cleared; score and ambiguity stay the forward values.
-__global__ __launch_bounds__(256) void k_match_cross_filter(surfhip_point* pts1, const int* __restrict__ counts1,
-                                                            int slots1, int slots2, const u64* __restrict__ back)
+__global__ __launch_bounds__(256) void k_match_cross_filter(const MatchBatch mb)
 {
-    const int pair = blockIdx.y;
+    const int* __restrict__ counts1 = mb.counts1;
+    const u64* __restrict__ back = mb.back;
+    const int pair = blockIdx.y, slots1 = mb.slots1, slots2 = mb.slots2;
     const int p1 = blockIdx.x * 256 + threadIdx.x;
     if (p1 >= clamp_count(counts1[pair], slots1)) return;
-    surfhip_point& q = pts1[(size_t)pair * slots1 + p1];
+    surfhip_point& q = mb.pts1[(size_t)pair * slots1 + p1];
     const int m = q.match;
     if (m < 0 || m >= slots2) return;                       // (the forward pass writes -1 or an index below n2)
     if ((uint32_t)back[(size_t)pair * slots2 + m] == ~(uint32_t)p1) return;
@@ -854,31 +827,31 @@ __global__ __launch_bounds__(256) void k_match_cross_filter(surfhip_point* pts1,
 
 }  // namespace
 
+// The chunks k_match_part's grid.y splits n2 set-2 points into.
+static int match_chunks(int n2, int flags)
+{
+    const int ntile = (scanned(n2, flags) + 31) / 32;
+    return (ntile + kTilesPerChunk - 1) / kTilesPerChunk;
+}
+
 size_t match_scratch_bytes(int n1, int n2, int flags)
 {
-    const int nscan = (flags & SURFHIP_MATCH_FULL_TAIL) ? n2 : 32 * (n2 / 32);
-    const int ntile = (nscan + 31) / 32;
-    const int nchunk = ntile > 0 ? (ntile + kTilesPerChunk - 1) / kTilesPerChunk : 0;
-    return (size_t)nchunk * 8 * (size_t)n1 * 12;
+    return (size_t)match_chunks(n2, flags) * 8 * (size_t)n1 * 12;
 }
 
 hipError_t launch_match(surfhip_point* pts1, const surfhip_point* pts2, const float* f1, const float* f2, int n1,
                         int n2, int nf, int flags, void* scratch, hipStream_t s)
 {
-    const int nscan = (flags & SURFHIP_MATCH_FULL_TAIL) ? n2 : 32 * (n2 / 32);
+    const int nscan = scanned(n2, flags);
     const int ntile = (nscan + 31) / 32;
-    const int nchunk = ntile > 0 ? (ntile + kTilesPerChunk - 1) / kTilesPerChunk : 0;
+    const int nchunk = match_chunks(n2, flags);
     float* pmx = static_cast<float*>(scratch);
     float* psc = pmx + (size_t)nchunk * 8 * n1;
     int* pix = reinterpret_cast<int*>(psc + (size_t)nchunk * 8 * n1);
     if (nchunk > 0) {
         const dim3 grid((n1 + kMatchThreads - 1) / kMatchThreads, nchunk);
-        if (nf == 64)
-            k_match_part<64><<<grid, kMatchThreads, 0, s>>>(f1, f2, n1, nscan, ntile, pmx, psc, pix);
-        else if (nf == 128)
-            k_match_part<128><<<grid, kMatchThreads, 0, s>>>(f1, f2, n1, nscan, ntile, pmx, psc, pix);
-        else
-            k_match_part_any<<<grid, kMatchThreads, 0, s>>>(f1, f2, n1, nf, nscan, ntile, pmx, psc, pix);
+        const auto part = nf == 64 ? k_match_part<64> : nf == 128 ? k_match_part<128> : k_match_part<0>;
+        part<<<grid, kMatchThreads, 0, s>>>(f1, f2, n1, nscan, ntile, pmx, psc, pix, nf);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -886,149 +859,84 @@ hipError_t launch_match(surfhip_point* pts1, const surfhip_point* pts2, const fl
     return hipGetLastError();
 }
 
-template <bool LAP, bool CROSS, int MODE>
-static void launch_match_batch_lap(dim3 grid, surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
-                                   const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
-                                   int nf, int full_tail, u64* back, const float4* boxes, int tiles,
-                                   const surfhip_match_window& win, const float* hm, int h_stride, hipStream_t s)
+// The batch kernel of (mode, mutual, same laplace, nf): the template axes from
+// the run-time values, one per step.
+using BatchKernel = void (*)(MatchBatch);
+template <int MODE = -1, int CROSS = -1, int LAP = -1>
+static BatchKernel batch_kernel(int mode, bool cross, bool lap, int nf)
 {
-    if (nf == 64)
-        k_match_batch<64, LAP, CROSS, MODE><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2,
-                                                                           counts2, slots2, full_tail, back, boxes,
-                                                                           tiles, win, hm, h_stride);
-    else if (nf == 128)
-        k_match_batch<128, LAP, CROSS, MODE><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2,
-                                                                            counts2, slots2, full_tail, back, boxes,
-                                                                            tiles, win, hm, h_stride);
+    if constexpr (MODE < 0)
+        return mode == MATCH_PLAIN    ? batch_kernel<MATCH_PLAIN>(mode, cross, lap, nf)
+               : mode == MATCH_WINDOW ? batch_kernel<MATCH_WINDOW>(mode, cross, lap, nf)
+                                      : batch_kernel<MATCH_GUIDED>(mode, cross, lap, nf);
+    else if constexpr (CROSS < 0)
+        return cross ? batch_kernel<MODE, 1>(mode, cross, lap, nf) : batch_kernel<MODE, 0>(mode, cross, lap, nf);
+    else if constexpr (LAP < 0)
+        return lap ? batch_kernel<MODE, CROSS, 1>(mode, cross, lap, nf)
+                   : batch_kernel<MODE, CROSS, 0>(mode, cross, lap, nf);
     else
-        k_match_batch_any<LAP, CROSS, MODE><<<grid, kBatchThreads, 0, s>>>(pts1, f1, counts1, slots1, pts2, f2,
-                                                                           counts2, slots2, nf, full_tail, back,
-                                                                           boxes, tiles, win, hm, h_stride);
+        return nf == 64    ? k_match_batch<64, LAP != 0, CROSS != 0, MODE>
+               : nf == 128 ? k_match_batch<128, LAP != 0, CROSS != 0, MODE>
+                           : k_match_batch_any<LAP != 0, CROSS != 0, MODE>;
 }
 
+// The scratch of a batched match: the tile boxes (not MATCH_PLAIN), then the
+// keys (SURFHIP_MATCH_MUTUAL).
 static int match_window_tiles(int slots2) { return (slots2 + 31) / 32; }
 
-// back == nullptr: the forward match alone.  Otherwise back[npairs][slots2]
-// keys, zero on entry, get the back direction's best and the filter pass
-// follows each launch (the kernel boundary makes the keys visible to it).
-// WIN: boxes[npairs][match_window_tiles(slots2)] are written ahead of each
-// launch, in any state on entry.  GUIDED: pair i's matrix is the nine floats at
-// hm + i * h_stride (device memory).
-template <bool CROSS, int MODE>
-static hipError_t launch_match_batch_pass(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
-                                          const surfhip_point* pts2, const float* f2, const int* counts2,
-                                          int slots2, int npairs, int nf, int flags, u64* back, float4* boxes,
-                                          const surfhip_match_window& win, const float* hm, int h_stride,
-                                          hipStream_t s)
+static size_t match_box_bytes(int mode, int npairs, int slots2)
 {
-    constexpr bool WIN = MODE != MATCH_PLAIN;
-    const int full_tail = (flags & SURFHIP_MATCH_FULL_TAIL) ? 1 : 0;
-    const int tiles = match_window_tiles(slots2);
-    constexpr int kMaxGridY = 65535;                        // one launch up to this many pairs
-    for (int p0 = 0; p0 < npairs; p0 += kMaxGridY) {
-        const int np = npairs - p0 < kMaxGridY ? npairs - p0 : kMaxGridY;
-        const dim3 grid((slots1 + kBatchPts - 1) / kBatchPts, np);
-        surfhip_point* a = pts1 + (size_t)p0 * slots1;
-        const surfhip_point* b = pts2 + (size_t)p0 * slots2;
-        const float* fa = f1 + (size_t)p0 * slots1 * nf;
-        const float* fb = f2 + (size_t)p0 * slots2 * nf;
-        u64* bk = CROSS ? back + (size_t)p0 * slots2 : nullptr;
-        float4* bx = WIN ? boxes + (size_t)p0 * tiles : nullptr;
-        const float* hp = MODE == MATCH_GUIDED ? hm + (size_t)p0 * h_stride : nullptr;
-        if (WIN) {
-            k_match_tile_boxes<<<dim3((tiles + 7) / 8, np), 256, 0, s>>>(b, counts2 + p0, slots2, full_tail, tiles, bx);
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return e;
-        }
-        if (flags & SURFHIP_MATCH_SAME_LAPLACE)
-            launch_match_batch_lap<true, CROSS, MODE>(grid, a, fa, counts1 + p0, slots1, b, fb, counts2 + p0, slots2,
-                                                      nf, full_tail, bk, bx, tiles, win, hp, h_stride, s);
-        else
-            launch_match_batch_lap<false, CROSS, MODE>(grid, a, fa, counts1 + p0, slots1, b, fb, counts2 + p0, slots2,
-                                                       nf, full_tail, bk, bx, tiles, win, hp, h_stride, s);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        if (CROSS) {
-            k_match_cross_filter<<<dim3((slots1 + 255) / 256, np), 256, 0, s>>>(a, counts1 + p0, slots1, slots2, bk);
-            e = hipGetLastError();
-            if (e != hipSuccess) return e;
-        }
-    }
-    return hipSuccess;
+    return mode != MATCH_PLAIN ? sizeof(float4) * (size_t)npairs * (size_t)match_window_tiles(slots2) : 0;
 }
 
-hipError_t launch_match_batch(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
-                              const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
-                              int npairs, int nf, int flags, hipStream_t s)
+static size_t match_key_bytes(int npairs, int slots2, int flags)
 {
-    return launch_match_batch_pass<false, MATCH_PLAIN>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs,
-                                                       nf, flags, nullptr, nullptr, {}, nullptr, 0, s);
+    return (flags & SURFHIP_MATCH_MUTUAL) ? sizeof(u64) * (size_t)npairs * (size_t)slots2 : 0;
 }
 
-size_t match_batch_cross_scratch_bytes(int npairs, int slots2)
-{
-    return npairs > 0 && slots2 > 0 ? sizeof(u64) * (size_t)npairs * (size_t)slots2 : 0;
-}
-
-hipError_t launch_match_batch_cross(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
-                                    const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
-                                    int npairs, int nf, int flags, void* scratch, hipStream_t s)
-{
-    const hipError_t e = hipMemsetAsync(scratch, 0, match_batch_cross_scratch_bytes(npairs, slots2), s);
-    if (e != hipSuccess) return e;
-    return launch_match_batch_pass<true, MATCH_PLAIN>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs,
-                                                      nf, flags, static_cast<u64*>(scratch), nullptr, {}, nullptr, 0,
-                                                      s);
-}
-
-// Scratch of the windowed match: the tile boxes, 16 B per (pair, 32 slots of
-// set 2), then with SURFHIP_MATCH_MUTUAL the keys of the mutual-best test.
-static size_t match_window_box_bytes(int npairs, int slots2)
-{
-    return sizeof(float4) * (size_t)npairs * (size_t)match_window_tiles(slots2);
-}
-
-size_t match_batch_window_scratch_bytes(int npairs, int slots2, int flags)
+size_t match_batch_scratch_bytes(int mode, int npairs, int slots2, int flags)
 {
     if (npairs <= 0 || slots2 <= 0) return 0;
-    return match_window_box_bytes(npairs, slots2) +
-           ((flags & SURFHIP_MATCH_MUTUAL) ? match_batch_cross_scratch_bytes(npairs, slots2) : 0);
+    return match_box_bytes(mode, npairs, slots2) + match_key_bytes(npairs, slots2, flags);
 }
 
-// The windowed (hm == nullptr) and the guided match: one scratch layout.
-template <int MODE>
-static hipError_t launch_match_batch_boxed(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
-                                           const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
-                                           int npairs, int nf, int flags, const surfhip_match_window& win,
-                                           const float* hm, int h_stride, void* scratch, hipStream_t s)
+// Per launch of up to 65,535 pairs (grid.y): the boxes of set 2's tiles (not
+// MATCH_PLAIN; in any state on entry), the batch kernel, and with
+// SURFHIP_MATCH_MUTUAL the filter pass over the keys the batch kernel left (the
+// kernel boundary makes them visible to it; zero on entry).
+hipError_t launch_match_batch(const MatchBatch& in, int mode, void* scratch, hipStream_t s)
 {
-    float4* boxes = static_cast<float4*>(scratch);
-    if (!(flags & SURFHIP_MATCH_MUTUAL))
-        return launch_match_batch_pass<false, MODE>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf,
-                                                    flags, nullptr, boxes, win, hm, h_stride, s);
-    u64* back = reinterpret_cast<u64*>(static_cast<char*>(scratch) + match_window_box_bytes(npairs, slots2));
-    const hipError_t e = hipMemsetAsync(back, 0, match_batch_cross_scratch_bytes(npairs, slots2), s);
-    if (e != hipSuccess) return e;
-    return launch_match_batch_pass<true, MODE>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf,
-                                               flags, back, boxes, win, hm, h_stride, s);
-}
-
-hipError_t launch_match_batch_window(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
-                                     const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
-                                     int npairs, int nf, int flags, const surfhip_match_window& win, void* scratch,
-                                     hipStream_t s)
-{
-    return launch_match_batch_boxed<MATCH_WINDOW>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf,
-                                                  flags, win, nullptr, 0, scratch, s);
-}
-
-hipError_t launch_match_batch_guided(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
-                                     const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
-                                     int npairs, int nf, int flags, const float* hm, int h_stride,
-                                     const surfhip_match_window& win, void* scratch, hipStream_t s)
-{
-    return launch_match_batch_boxed<MATCH_GUIDED>(pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf,
-                                                  flags, win, hm, h_stride, scratch, s);
+    const bool cross = (in.flags & SURFHIP_MATCH_MUTUAL) != 0, win = mode != MATCH_PLAIN;
+    MatchBatch all = in;
+    all.tiles = match_window_tiles(in.slots2);
+    all.boxes = win ? static_cast<float4*>(scratch) : nullptr;
+    all.back = nullptr;
+    if (cross) {
+        all.back = reinterpret_cast<u64*>(static_cast<char*>(scratch) + match_box_bytes(mode, in.npairs, in.slots2));
+        const hipError_t e = hipMemsetAsync(all.back, 0, match_key_bytes(in.npairs, in.slots2, in.flags), s);
+        if (e != hipSuccess) return e;
+    }
+    const BatchKernel kernel = batch_kernel(mode, cross, (in.flags & SURFHIP_MATCH_SAME_LAPLACE) != 0, in.nf);
+    constexpr int kMaxGridY = 65535;
+    for (int p0 = 0; p0 < in.npairs; p0 += kMaxGridY) {
+        const MatchBatch b = all.from(p0);
+        const int np = b.npairs < kMaxGridY ? b.npairs : kMaxGridY;
+        hipError_t e = hipSuccess;
+        if (win) {
+            k_match_tile_boxes<<<dim3((b.tiles + 7) / 8, np), 256, 0, s>>>(b);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) {
+            kernel<<<dim3((b.slots1 + kBatchPts - 1) / kBatchPts, np), kBatchThreads, 0, s>>>(b);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess && cross) {
+            k_match_cross_filter<<<dim3((b.slots1 + 255) / 256, np), 256, 0, s>>>(b);
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 }  // namespace surfhip

@@ -8,55 +8,10 @@ import functools
 import numpy as np
 import pytest
 
+from match_ref import (CANARY, COUNTS1, COUNTS2, FULL_TAIL, KEPT_FIELDS, MATCH_FIELDS, SAME_LAPLACE, assert_match_equal,
+                       make_points, ragged_data, run_batch, with_canary)
+
 pytestmark = pytest.mark.gpu
-
-MATCH_FIELDS = ("score", "match", "match_x", "match_y", "ambiguity")
-KEPT_FIELDS = ("x", "y", "scale", "o", "strength", "laplace", "ori")
-CANARY = {"score": np.float32(-77.5), "match": np.int32(-12345), "match_x": np.float32(3.0e30),
-          "match_y": np.float32(-4.0e30), "ambiguity": np.float32(55.25)}
-FULL_TAIL, SAME_LAPLACE = 1, 2
-
-COUNTS1 = (0, 1, 31, 32, 33, 63, 64, 65, 97, 128, 159, 160)
-COUNTS2 = (100, 0, 31, 32, 33, 64, 65, 95, 96, 191, 192, 7)
-SLOTS1, SLOTS2 = 160, 192
-
-
-def assert_match_equal(got, ref, what=""):
-    for f in MATCH_FIELDS:
-        g, r = got[f], ref[f]
-        if g.dtype == np.float32:
-            g, r = g.view(np.uint32), r.view(np.uint32)
-        bad = np.nonzero(g != r)[0]
-        assert len(bad) == 0, f"{what}{f} differs at {bad[:5]}: {got[f][bad[:5]]} vs {ref[f][bad[:5]]}"
-
-
-def with_canary(pts):
-    out = pts.copy()
-    for f, v in CANARY.items():
-        out[f] = v
-    return out
-
-
-def run_batch(surf, p1, f1, c1, p2, f2, c2, flags=0):
-    """Upload [npairs][slots] arrays, one surfhip_match_batch call; returns
-    the downloaded (pts1, desc1, desc2)."""
-    npairs, s1 = p1.shape
-    s2 = p2.shape[1]
-    nf = f1.shape[2]
-    bufs = []
-    for a in (p1, f1, np.asarray(c1, np.int32), p2, f2, np.asarray(c2, np.int32)):
-        b = surf.DeviceBuffer(max(a.nbytes, 4))
-        b.upload(a)
-        bufs.append(b)
-    surf.match_batch(bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, s1, bufs[3].ptr, bufs[4].ptr, bufs[5].ptr, s2, npairs,
-                     nf, flags)
-    surf.synchronize()
-    got = bufs[0].download(surf.POINT_DTYPE, npairs * s1).reshape(npairs, s1)
-    d1 = bufs[1].download(np.float32, f1.size).reshape(f1.shape)
-    d2 = bufs[4].download(np.float32, f2.size).reshape(f2.shape)
-    for b in bufs:
-        b.free()
-    return got, d1, d2
 
 
 def check_batch(surf, orc, p1, f1, c1, p2, f2, c2, flags, got=None, ref_fn=None):
@@ -78,39 +33,6 @@ def check_batch(surf, orc, p1, f1, c1, p2, f2, c2, flags, got=None, ref_fn=None)
         for f in KEPT_FIELDS:
             assert (got[i][f].view(np.uint32) == p1[i][f].view(np.uint32)).all(), (i, f)
     return got
-
-
-def make_points(rng, npairs, slots, dtype):
-    p = np.zeros((npairs, slots), dtype)
-    p["x"] = rng.uniform(0, 1920, (npairs, slots))
-    p["y"] = rng.uniform(0, 1080, (npairs, slots))
-    p["scale"] = rng.uniform(1, 9, (npairs, slots))
-    p["strength"] = rng.uniform(4, 900, (npairs, slots))
-    p["laplace"] = rng.choice(np.array([-1, 1], np.int32), (npairs, slots))
-    return p
-
-
-@functools.lru_cache(maxsize=None)
-def ragged_data(surf, nf):
-    """Case 2's batch: random normalised descriptors with a planted perfect
-    partner per pair; slots past the counts hold large descriptors that would
-    win every scan if they were read as points."""
-    rng = np.random.default_rng(1000 + nf)
-    npairs = len(COUNTS1)
-    f1 = rng.standard_normal((npairs, SLOTS1, nf)).astype(np.float32)
-    f2 = rng.standard_normal((npairs, SLOTS2, nf)).astype(np.float32)
-    f1 /= np.linalg.norm(f1, axis=2, keepdims=True)
-    f2 /= np.linalg.norm(f2, axis=2, keepdims=True)
-    for i, (n1, n2) in enumerate(zip(COUNTS1, COUNTS2)):
-        if n1 and n2:
-            f2[i, n2 // 2] = f1[i, 0]                             # a perfect partner (ties across rows)
-        f1[i, n1:] = 1000.0
-        f2[i, n2:] = 1000.0
-    p1 = with_canary(make_points(rng, npairs, SLOTS1, surf.POINT_DTYPE))
-    p2 = make_points(rng, npairs, SLOTS2, surf.POINT_DTYPE)
-    for a in (f1, f2, p1, p2):
-        a.setflags(write=False)
-    return p1, f1, p2, f2
 
 
 @functools.lru_cache(maxsize=None)

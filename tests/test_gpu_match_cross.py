@@ -10,116 +10,17 @@ oracle's own fp32 FMA chain, so the bits are the kernel's.  Back best: the
 first maximum of a column where that maximum is positive."""
 from __future__ import annotations
 
-import functools
-
 import numpy as np
 import pytest
 
-from test_gpu_match_batch import (CANARY, COUNTS1, COUNTS2, KEPT_FIELDS, MATCH_FIELDS, SLOTS1, SLOTS2,
-                                  assert_match_equal, make_points, ragged_data, with_canary)
+from match_ref import (CANARY, COUNTS1, COUNTS2, FULL_TAIL, KEPT_FIELDS, MATCH_FIELDS, SAME_LAPLACE, assert_match_equal,
+                       back_best, clamp, cross_model, make_points, matrices, ragged_data, ragged_matrices, ragged_plain,
+                       run_cross, score_column, with_canary)
 
 pytestmark = pytest.mark.gpu
 
-FULL_TAIL, SAME_LAPLACE = 1, 2
 
-
-# ------------------------------------------------------------------ model
-
-def clamp(c, slots):
-    return min(max(int(c), 0), slots)
-
-
-def score_column(orc, p1, f1, f2row):
-    """S(p1, j) for every p1 against the one set-2 descriptor f2row, where
-    positive (0 elsewhere, NaN scores included)."""
-    zero = np.zeros(1, p1.dtype)
-    return orc.match(p1, zero, f1, f2row[None], full_tail=True)["score"]
-
-
-def score_matrix(orc, p1, f1, f2):
-    s = np.zeros((len(p1), len(f2)), np.float32)
-    for j in range(len(f2)):
-        s[:, j] = score_column(orc, p1, f1, f2[j])
-    return s
-
-
-def forward_ref(orc, p1, p2, f1, f2, flags):
-    full = bool(flags & FULL_TAIL)
-    if not flags & SAME_LAPLACE:
-        return orc.match(p1, p2, f1, f2, full_tail=full)
-    ref = p1.copy()
-    for v in np.unique(p1["laplace"]):
-        fz = f2.copy()
-        fz[p2["laplace"] != v] = 0.0
-        rows = p1["laplace"] == v
-        ref[rows] = orc.match(p1, p2, f1, fz, full_tail=full)[rows]
-    return ref
-
-
-def back_best(s, p1, p2, flags):
-    """B(p2) for p2 < nscan from the score matrix s[n1][>= nscan]."""
-    n2 = len(p2)
-    nscan = n2 if flags & FULL_TAIL else 32 * (n2 // 32)
-    m = s[:, :nscan].copy()
-    if flags & SAME_LAPLACE:
-        m[p1["laplace"][:, None] != p2["laplace"][None, :nscan]] = 0.0
-    if m.shape[0] == 0 or nscan == 0:
-        return np.full(nscan, -1, np.int64)
-    return np.where(m.max(axis=0) > 0, m.argmax(axis=0), -1)
-
-
-def cross_model(orc, s, p1, p2, f1, f2, flags):
-    """(expected points, forward points) of one pair; s: its score matrix."""
-    fwd = forward_ref(orc, p1, p2, f1, f2, flags)
-    b = back_best(s, p1, p2, flags)
-    m = fwd["match"]
-    hit = m >= 0
-    rows = np.nonzero(hit)[0]
-    # the model agrees with itself: a forward score is the matrix entry, bitwise
-    assert (fwd["score"][rows].view(np.uint32) == s[rows, m[rows]].view(np.uint32)).all()
-    clear = hit.copy()
-    clear[rows] = b[m[rows]] != rows
-    out = fwd.copy()
-    out["match"][clear] = -1
-    out["match_x"][clear] = 0.0
-    out["match_y"][clear] = 0.0
-    return out, fwd
-
-
-# ---------------------------------------------------------------- running
-
-def run_cross(surf, p1, f1, c1, p2, f2, c2, flags=0, scratch=None, plain=False):
-    """Upload [npairs][slots] arrays, one call (match_batch_cross, or
-    match_batch with plain); returns the downloaded set-1 points after the
-    checks that neither descriptor array nor set 2 changed."""
-    npairs, s1 = p1.shape
-    s2 = p2.shape[1]
-    nf = f1.shape[2]
-    bufs = []
-    for a in (p1, f1, np.asarray(c1, np.int32), p2, f2, np.asarray(c2, np.int32)):
-        b = surf.DeviceBuffer(max(a.nbytes, 4))
-        b.upload(a)
-        bufs.append(b)
-    args = (bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, s1, bufs[3].ptr, bufs[4].ptr, bufs[5].ptr, s2, npairs, nf)
-    if plain:
-        surf.match_batch(*args, flags)
-    else:
-        own = scratch is None
-        if own:
-            scratch = surf.DeviceBuffer(surf.match_batch_cross_scratch_bytes(npairs, s1, s2))
-        assert scratch.nbytes >= surf.match_batch_cross_scratch_bytes(npairs, s1, s2)
-        surf.match_batch_cross(*args, scratch.ptr, flags)
-    surf.synchronize()
-    got = bufs[0].download(surf.POINT_DTYPE, npairs * s1).reshape(npairs, s1)
-    assert bufs[1].download(np.float32, f1.size).tobytes() == f1.tobytes()
-    assert bufs[4].download(np.float32, f2.size).tobytes() == f2.tobytes()
-    assert bufs[3].download(surf.POINT_DTYPE, npairs * s2).tobytes() == p2.tobytes()
-    for b in bufs:
-        b.free()
-    if not plain and own:
-        scratch.free()
-    return got
-
+# ---------------------------------------------------------------- checking
 
 def check_cross(orc, got, p1, f1, c1, p2, f2, c2, flags, mats):
     """got against the model per pair + the nothing-else-written properties
@@ -137,24 +38,6 @@ def check_cross(orc, got, p1, f1, c1, p2, f2, c2, flags, mats):
             assert (got[i][f].view(np.uint32) == p1[i][f].view(np.uint32)).all(), (i, f)
         refs.append((ref, fwd))
     return refs
-
-
-def matrices(orc, p1, f1, c1, f2, c2):
-    s1, s2 = p1.shape[1], f2.shape[1]
-    return [score_matrix(orc, p1[i, :clamp(c1[i], s1)], f1[i, :clamp(c1[i], s1)], f2[i, :clamp(c2[i], s2)])
-            for i in range(len(p1))]
-
-
-@functools.lru_cache(maxsize=None)
-def ragged_matrices(surf, orc, nf):
-    p1, f1, p2, f2 = ragged_data(surf, nf)
-    return matrices(orc, p1, f1, COUNTS1, f2, COUNTS2)
-
-
-@functools.lru_cache(maxsize=None)
-def ragged_plain(surf, nf, flags):
-    p1, f1, p2, f2 = ragged_data(surf, nf)
-    return run_cross(surf, p1, f1, COUNTS1, p2, f2, COUNTS2, flags, plain=True)
 
 
 # ------------------------------------------------------------------ tests

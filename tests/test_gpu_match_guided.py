@@ -5,7 +5,7 @@ every comparison is bitwise on the five match fields.
 The model needs no new oracle.  (u, v, W) of every set-1 point are computed
 in numpy float32 with exactly the kernel's operations; a copy of the set-1
 points with x, y replaced by u, v (NaN where W > 0 is false) goes to
-window_model / window_forward of test_gpu_match_window, which rest on
+window_model / window_forward of match_ref, which rest on
 or_match alone.  Only the five match fields are compared with that model;
 everything else is compared with the original upload."""
 from __future__ import annotations
@@ -15,16 +15,14 @@ import functools
 import numpy as np
 import pytest
 
-from test_gpu_match_batch import (CANARY, COUNTS1, COUNTS2, KEPT_FIELDS, MATCH_FIELDS, assert_match_equal, make_points,
-                                  ragged_data, with_canary)
-from test_gpu_match_cross import clamp, matrices, ragged_matrices, ragged_plain, run_cross, score_column
-from test_gpu_match_window import (EVERYWHERE, SYMMETRIC, WINDOWS, box, may_offer, offered_mask, run_window,
-                                   tile_census, window_data, window_forward, window_model)
+from match_ref import (CANARY, COUNTS1, COUNTS2, EVERYWHERE, FULL_TAIL, INF, KEPT_FIELDS, MATCH_FIELDS, MUTUAL,
+                       SAME_LAPLACE, SYMMETRIC, WINDOWS, assert_match_equal, box, clamp, make_points, matrices,
+                       may_offer, offered_mask, ragged_data, ragged_matrices, ragged_plain, run_cross, run_guided,
+                       run_window, score_column, small_batch, tile_census, window_data, window_forward, window_model,
+                       with_canary)
 
 pytestmark = pytest.mark.gpu
 
-FULL_TAIL, SAME_LAPLACE, MUTUAL = 1, 2, 4
-INF = float("inf")
 IDENTITY = (1, 0, 0, 0, 1, 0, 0, 0, 1)
 TIGHT = (-8.0, 8.0, -8.0, 8.0)
 
@@ -85,40 +83,6 @@ def pack_h(hs, stride):
 
 
 # ---------------------------------------------------------------- running
-
-def run_guided(surf, p1, f1, c1, p2, f2, c2, flags, win, hbuf, stride, scratch=None):
-    """Upload [npairs][slots] arrays and the matrices, one match_batch_guided
-    call; returns the downloaded set-1 points after the checks that neither
-    descriptor array, nor set 2, nor the matrices changed."""
-    npairs, s1 = p1.shape
-    s2 = p2.shape[1]
-    nf = f1.shape[2]
-    hbuf = np.ascontiguousarray(hbuf, np.float32)
-    bufs = []
-    for a in (p1, f1, np.asarray(c1, np.int32), p2, f2, np.asarray(c2, np.int32), hbuf):
-        b = surf.DeviceBuffer(max(a.nbytes, 4))
-        b.upload(a)
-        bufs.append(b)
-    own = scratch is None
-    need = surf.match_batch_guided_scratch_bytes(npairs, s1, s2, flags)
-    assert need == surf.match_batch_window_scratch_bytes(npairs, s1, s2, flags)
-    if own:
-        scratch = surf.DeviceBuffer(need)
-    assert scratch.nbytes >= need
-    surf.match_batch_guided(bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, s1, bufs[3].ptr, bufs[4].ptr, bufs[5].ptr, s2,
-                            npairs, nf, flags, bufs[6].ptr, stride, win, scratch.ptr)
-    surf.synchronize()
-    got = bufs[0].download(surf.POINT_DTYPE, npairs * s1).reshape(npairs, s1)
-    assert bufs[1].download(np.float32, f1.size).tobytes() == f1.tobytes()
-    assert bufs[4].download(np.float32, f2.size).tobytes() == f2.tobytes()
-    assert bufs[3].download(surf.POINT_DTYPE, npairs * s2).tobytes() == p2.tobytes()
-    assert bufs[6].download(np.float32, hbuf.size).tobytes() == hbuf.tobytes()
-    for b in bufs:
-        b.free()
-    if own:
-        scratch.free()
-    return got
-
 
 def check_guided(orc, got, p1, f1, c1, p2, f2, c2, flags, win, mats, hs, fwds=None):
     """got against the model per pair (hs[i]: the pair's matrix) + the
@@ -489,20 +453,6 @@ def test_more_tiles_than_one_list_chunk(surf, orc):
 
 
 # ------------------------------------------------------------ 6. robustness
-
-def small_batch(surf, seed, npairs, s1, s2, nf=64):
-    rng = np.random.default_rng(seed)
-    f1 = rng.standard_normal((npairs, s1, nf)).astype(np.float32)
-    f2 = rng.standard_normal((npairs, s2, nf)).astype(np.float32)
-    f1 /= np.linalg.norm(f1, axis=2, keepdims=True)
-    f2 /= np.linalg.norm(f2, axis=2, keepdims=True)
-    p1 = with_canary(make_points(rng, npairs, s1, surf.POINT_DTYPE))
-    p2 = make_points(rng, npairs, s2, surf.POINT_DTYPE)
-    for p in (p1, p2):
-        p["x"] = rng.uniform(0, 120, p.shape)
-        p["y"] = np.sort(rng.uniform(0, 300, p.shape), axis=1)
-    return rng, p1, f1, p2, f2
-
 
 def test_scratch_full_of_ff(surf, orc):
     """The scratch may hold anything: all-0xFF first, then its own leftovers."""

@@ -9,7 +9,7 @@ set 2 with the descriptor rows of the points not offered to p1 set to zero
 (the zero-row construction of test_gpu_match_batch.test_same_laplace_flag,
 here per point; points with one and the same offered set share one or_match
 call, which treats its set-1 points independently).  Back: the column maxima
-of the score matrix of test_gpu_match_cross.score_column, masked by
+of the score matrix of match_ref.score_column, masked by
 "offered"."""
 from __future__ import annotations
 
@@ -18,148 +18,16 @@ import functools
 import numpy as np
 import pytest
 
-from test_gpu_match_batch import (CANARY, COUNTS1, COUNTS2, KEPT_FIELDS, MATCH_FIELDS, SLOTS1, SLOTS2,
-                                  assert_match_equal, make_points, ragged_data, with_canary)
-from test_gpu_match_cross import (clamp, cross_model, forward_ref, matrices, ragged_matrices, ragged_plain, run_cross,
-                                  score_column)
+from match_ref import (CANARY, COUNTS1, COUNTS2, EVERYWHERE, FULL_TAIL, INF, KEPT_FIELDS, MATCH_FIELDS, MUTUAL,
+                       SAME_LAPLACE, SYMMETRIC, WINDOWS, assert_match_equal, box, clamp, cross_model, forward_ref,
+                       make_points, matrices, may_offer, offered_mask, ragged_data, ragged_matrices, ragged_plain,
+                       run_cross, run_window, score_column, tile_census, window_data, window_forward, window_model,
+                       with_canary)
 
 pytestmark = pytest.mark.gpu
 
-FULL_TAIL, SAME_LAPLACE, MUTUAL = 1, 2, 4
-INF = float("inf")
-EVERYWHERE = (-INF, INF, -INF, INF)
-SYMMETRIC = (-40.0, 40.0, -40.0, 40.0)
-STEREO = (-64.0, 0.0, -1.5, 1.5)
-WINDOWS = {"symmetric": SYMMETRIC, "stereo": STEREO}
 
-
-# ------------------------------------------------------------------ model
-
-def offered_mask(p1, p2, flags, win):
-    """[n1][n2]: set-2 point p2 is offered to set-1 point p1 (the scan limit
-    nscan apart, which or_match applies itself)."""
-    w = np.asarray(win, np.float32)
-    with np.errstate(invalid="ignore"):
-        dx = p2["x"][None, :] - p1["x"][:, None]                  # one fp32 subtraction each
-        dy = p2["y"][None, :] - p1["y"][:, None]
-        m = (dx >= w[0]) & (dx <= w[1]) & (dy >= w[2]) & (dy <= w[3])
-    assert dx.dtype == np.float32
-    if flags & SAME_LAPLACE:
-        m &= p1["laplace"][:, None] == p2["laplace"][None, :]
-    return m
-
-
-def window_forward(orc, p1, p2, f1, f2, flags, win):
-    """(forward points, offered mask) of one pair."""
-    m = offered_mask(p1, p2, flags, win)
-    ref = p1.copy()
-    if len(p1) == 0:
-        return ref, m
-    groups, inv = np.unique(m, axis=0, return_inverse=True)
-    inv = inv.reshape(-1)
-    for g in range(len(groups)):
-        fz = f2.copy()
-        fz[~groups[g]] = 0.0
-        rows = inv == g
-        ref[rows] = orc.match(p1[rows], p2, f1[rows], fz, full_tail=bool(flags & FULL_TAIL))
-    return ref, m
-
-
-def window_model(orc, s, p1, p2, f1, f2, flags, win, known=None):
-    """(expected points, forward points, offered mask) of one pair; s: its
-    score matrix (needed with MUTUAL only); known: its window_forward result
-    where there is one already."""
-    fwd, m = known if known is not None else window_forward(orc, p1, p2, f1, f2, flags, win)
-    if not flags & MUTUAL:
-        return fwd, fwd, m
-    n2 = len(p2)
-    nscan = n2 if flags & FULL_TAIL else 32 * (n2 // 32)
-    ms = np.where(m[:, :nscan], s[:, :nscan], np.float32(0))
-    if ms.shape[0] == 0 or nscan == 0:
-        b = np.full(nscan, -1, np.int64)
-    else:
-        b = np.where(ms.max(axis=0) > 0, ms.argmax(axis=0), -1)
-    hit = fwd["match"] >= 0
-    rows = np.nonzero(hit)[0]
-    cols = fwd["match"][rows]
-    assert m[rows, cols].all()                                    # a match is an offered point ...
-    assert (fwd["score"][rows].view(np.uint32) == s[rows, cols].view(np.uint32)).all()   # ... with the matrix's score
-    clear = hit.copy()
-    clear[rows] = b[cols] != rows
-    out = fwd.copy()
-    out["match"][clear] = -1
-    out["match_x"][clear] = 0.0
-    out["match_y"][clear] = 0.0
-    return out, fwd, m
-
-
-def box(x, y):
-    """(xmin, xmax, ymin, ymax), NaN ignored; of nothing: (inf, -inf, inf, -inf)."""
-    return (np.fmin.reduce(x, initial=np.float32(INF)), np.fmax.reduce(x, initial=np.float32(-INF)),
-            np.fmin.reduce(y, initial=np.float32(INF)), np.fmax.reduce(y, initial=np.float32(-INF)))
-
-
-def may_offer(a, b, win):
-    """The conservative fp32 box test: may a point of box a (set 1) be
-    offered a point of box b (set 2)?"""
-    w = np.asarray(win, np.float32)
-    with np.errstate(invalid="ignore"):
-        return bool(not b[0] - a[1] > w[1] and not b[1] - a[0] < w[0] and not b[2] - a[3] > w[3]
-                    and not b[3] - a[2] < w[2])
-
-
-def tile_census(p1, p2, flags, win, m, group=128):
-    """Over the (group of set-1 points, set-2 tile) combinations of one pair:
-    (combinations, kept by the box test, kept with some but not all pairs
-    offered).  Asserts the box test's promise: a dropped one offers nothing."""
-    n2 = len(p2)
-    nscan = n2 if flags & FULL_TAIL else 32 * (n2 // 32)
-    total = kept = partial = 0
-    for g0 in range(0, len(p1), group):
-        a = box(p1["x"][g0:g0 + group], p1["y"][g0:g0 + group])
-        for t0 in range(0, nscan, 32):
-            t1 = min(t0 + 32, nscan)
-            sub = m[g0:g0 + group, t0:t1]
-            keep = may_offer(a, box(p2["x"][t0:t1], p2["y"][t0:t1]), win)
-            assert keep or not sub.any()
-            total += 1
-            kept += keep
-            partial += bool(keep and sub.any() and not sub.all())
-    return total, kept, partial
-
-
-# ---------------------------------------------------------------- running
-
-def run_window(surf, p1, f1, c1, p2, f2, c2, flags, win, scratch=None):
-    """Upload [npairs][slots] arrays, one match_batch_window call; returns the
-    downloaded set-1 points after the checks that neither descriptor array
-    nor set 2 changed."""
-    npairs, s1 = p1.shape
-    s2 = p2.shape[1]
-    nf = f1.shape[2]
-    bufs = []
-    for a in (p1, f1, np.asarray(c1, np.int32), p2, f2, np.asarray(c2, np.int32)):
-        b = surf.DeviceBuffer(max(a.nbytes, 4))
-        b.upload(a)
-        bufs.append(b)
-    own = scratch is None
-    need = surf.match_batch_window_scratch_bytes(npairs, s1, s2, flags)
-    if own:
-        scratch = surf.DeviceBuffer(need)
-    assert scratch.nbytes >= need
-    surf.match_batch_window(bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, s1, bufs[3].ptr, bufs[4].ptr, bufs[5].ptr, s2,
-                            npairs, nf, flags, win, scratch.ptr)
-    surf.synchronize()
-    got = bufs[0].download(surf.POINT_DTYPE, npairs * s1).reshape(npairs, s1)
-    assert bufs[1].download(np.float32, f1.size).tobytes() == f1.tobytes()
-    assert bufs[4].download(np.float32, f2.size).tobytes() == f2.tobytes()
-    assert bufs[3].download(surf.POINT_DTYPE, npairs * s2).tobytes() == p2.tobytes()
-    for b in bufs:
-        b.free()
-    if own:
-        scratch.free()
-    return got
-
+# ---------------------------------------------------------------- checking
 
 def check_window(orc, got, p1, f1, c1, p2, f2, c2, flags, win, mats, fwds=None):
     """got against the model per pair + the nothing-else-written properties of
@@ -179,25 +47,6 @@ def check_window(orc, got, p1, f1, c1, p2, f2, c2, flags, win, mats, fwds=None):
             assert (got[i][f].view(np.uint32) == p1[i][f].view(np.uint32)).all(), (i, f)
         refs.append((ref, fwd, m))
     return refs
-
-
-@functools.lru_cache(maxsize=None)
-def window_data(surf, nf):
-    """The ragged batch of test_gpu_match_batch with coordinates for windows:
-    set 2 sorted by y inside every pair (32 consecutive points: a band of
-    about 100 rows), set 1 sorted in the even pairs and in random order in the
-    odd ones (a block of those covers everything: nothing to skip)."""
-    rp1, f1, rp2, f2 = ragged_data(surf, nf)
-    rng = np.random.default_rng(2000 + nf)
-    p1, p2 = rp1.copy(), rp2.copy()
-    for p, slots in ((p1, SLOTS1), (p2, SLOTS2)):
-        p["x"] = rng.uniform(0, 160, (len(p), slots)).astype(np.float32)
-        p["y"] = np.sort(np.round(rng.uniform(0, 600, (len(p), slots)) * 2) / 2, axis=1).astype(np.float32)
-    for i in range(1, len(p1), 2):
-        p1["y"][i] = p1["y"][i][rng.permutation(SLOTS1)]
-    for a in (p1, p2):
-        a.setflags(write=False)
-    return p1, f1, p2, f2
 
 
 @functools.lru_cache(maxsize=None)

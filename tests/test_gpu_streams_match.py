@@ -13,6 +13,7 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
+from match_ref import FULL_TAIL, SAME_LAPLACE, make_points, small_batch, with_canary
 from stream_ref import Streams, copy_async, late
 from test_gpu_fundamental import CAM_VERTICAL
 from test_gpu_fundamental import COUNTS as F_COUNTS
@@ -22,8 +23,6 @@ from test_gpu_homography import COUNTS as H_COUNTS
 from test_gpu_homography import H_PERSPECTIVE
 from test_gpu_homography import plant_pair as h_plant_pair
 from test_gpu_homography import ragged_data as h_ragged_data
-from test_gpu_match_batch import FULL_TAIL, SAME_LAPLACE, make_points, with_canary
-from test_gpu_match_guided import small_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -99,7 +98,7 @@ def test_control_homography_batch_on_another_stream_is_seen(surf, where):
 @pytest.mark.parametrize("own_scratch", [False, True], ids=["library-scratch", "caller-scratch"])
 @pytest.mark.parametrize("n1,n2,nf", [(70, 90, 64), (129, 333, 36)])
 def test_match(surf, n1, n2, nf, own_scratch):
-    """One pair; (129, 333, 36): k_match_part_any, more than one chunk of set 2 and the merge.  With the
+    """One pair; (129, 333, 36): k_match_part<0>, more than one chunk of set 2 and the merge.  With the
     library's scratch the call synchronises inside: it is the chain's last call."""
     rng = np.random.default_rng(5 + n1)
     f1 = rng.standard_normal((n1, nf)).astype(np.float32)
