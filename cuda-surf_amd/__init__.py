@@ -140,6 +140,9 @@ _sigs = {
     "surfhip_match_batch_window": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "surfhip_match_batch_guided_scratch": (_sz, [_i, _i, _i, _i]),
     "surfhip_match_batch_guided": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "surfhip_match_batch_epipolar_scratch": (_sz, [_i, _i, _i, _i]),
+    "surfhip_match_batch_epipolar": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, C.c_float, _vp, _vp,
+                                          _vp]),
     "surfhip_homography_batch": (_i, [_vp, _vp, _i, _i, C.c_float, C.c_float, _i, C.c_uint32, _vp, _vp, _vp]),
     "surfhip_homography_lds_capacity": (_i, []),
     "surfhip_fundamental_batch": (_i, [_vp, _vp, _i, _i, C.c_float, C.c_float, _i, C.c_uint32, _vp, _vp, _vp]),
@@ -651,7 +654,7 @@ def match_batch_cross(pts1_ptr: int, desc1_ptr: int, counts1_ptr: int, slots1: i
           "surfhip_match_batch_cross")
 
 
-MATCH_MUTUAL = 4            # match_batch_window and match_batch_guided only
+MATCH_MUTUAL = 4            # match_batch_window, _guided and _epipolar only
 
 
 class MatchWindow(C.Structure):
@@ -698,6 +701,27 @@ def match_batch_guided(pts1_ptr: int, desc1_ptr: int, counts1_ptr: int, slots1: 
     check(_lib.surfhip_match_batch_guided(pts1_ptr, desc1_ptr, counts1_ptr, slots1, pts2_ptr, desc2_ptr,
                                           counts2_ptr, slots2, npairs, nfeatures, flags, h_ptr, h_stride,
                                           C.byref(window), scratch_ptr, stream), "surfhip_match_batch_guided")
+
+
+def match_batch_epipolar_scratch_bytes(npairs: int, slots1: int, slots2: int, flags: int = 0) -> int:
+    return int(_lib.surfhip_match_batch_epipolar_scratch(npairs, slots1, slots2, flags))
+
+
+def match_batch_epipolar(pts1_ptr: int, desc1_ptr: int, counts1_ptr: int, slots1: int, pts2_ptr: int, desc2_ptr: int,
+                         counts2_ptr: int, slots2: int, npairs: int, nfeatures: int, flags: int, f_ptr: int,
+                         f_stride: int, band: float, window, scratch_ptr: int, stream=None) -> None:
+    """surfhip_match_batch_epipolar: match_batch_window over the set-2 points
+    that also lie within `band` pixels of each set-1 point's epipolar line
+    under its pair's fundamental matrix, the nine row-major floats at
+    f_ptr + 4 * i * f_stride in device memory (f_stride in floats: 16 for
+    fundamental_batch's records, 9 for packed matrices, 0 for one matrix
+    shared by all pairs).  scratch_ptr:
+    match_batch_epipolar_scratch_bytes(...) of device memory in any state."""
+    if not isinstance(window, MatchWindow):
+        window = MatchWindow(*window)
+    check(_lib.surfhip_match_batch_epipolar(pts1_ptr, desc1_ptr, counts1_ptr, slots1, pts2_ptr, desc2_ptr,
+                                            counts2_ptr, slots2, npairs, nfeatures, flags, f_ptr, f_stride, band,
+                                            C.byref(window), scratch_ptr, stream), "surfhip_match_batch_epipolar")
 
 
 # ------------------------------------------------------------ homography

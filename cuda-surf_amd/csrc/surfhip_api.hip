@@ -1186,9 +1186,10 @@ int surfhip_match(surfhip_point* pts1, const surfhip_point* pts2, const float* f
     return SURFHIP_OK;
 }
 
-// the checks the four batched match calls share; the scalars first, so that they are checked for npairs == 0 too.
-// b: the sets, npairs, nf and flags as the caller gave them (MATCH_GUIDED: hm, h_stride too); allowed: the call's
-// flag bits; window: required unless MATCH_PLAIN, and copied into b; scratch: checked where the call needs one
+// the checks the five batched match calls share; the scalars first, so that they are checked for npairs == 0 too.
+// b: the sets, npairs, nf and flags as the caller gave them (MATCH_GUIDED, MATCH_EPIPOLAR: hm, h_stride too;
+// MATCH_EPIPOLAR: band); allowed: the call's flag bits; window: required unless MATCH_PLAIN, and copied into b;
+// scratch: checked where the call needs one
 static int match_batch_args(MatchBatch& b, int allowed, int mode, const surfhip_match_window* window,
                             bool need_scratch, const void* scratch)
 {
@@ -1201,11 +1202,13 @@ static int match_batch_args(MatchBatch& b, int allowed, int mode, const surfhip_
             return SURFHIP_ERR_INVALID;
         b.win = *window;
     }
-    if (mode == MATCH_GUIDED && b.h_stride != 0 && b.h_stride < 9) return SURFHIP_ERR_INVALID;
+    const bool matrix = mode == MATCH_GUIDED || mode == MATCH_EPIPOLAR;
+    if (matrix && b.h_stride != 0 && b.h_stride < 9) return SURFHIP_ERR_INVALID;
+    if (mode == MATCH_EPIPOLAR && !(std::isfinite(b.band) && b.band >= 0.0f)) return SURFHIP_ERR_INVALID;
     if (b.npairs == 0) return SURFHIP_OK;
     if (!b.pts1 || !b.f1 || !b.counts1 || !b.pts2 || !b.f2 || !b.counts2) return SURFHIP_ERR_INVALID;
     if (need_scratch && (!scratch || ((uintptr_t)scratch & 15))) return SURFHIP_ERR_INVALID;
-    if (mode == MATCH_GUIDED && (!b.hm || ((uintptr_t)b.hm & 3))) return SURFHIP_ERR_INVALID;
+    if (matrix && (!b.hm || ((uintptr_t)b.hm & 3))) return SURFHIP_ERR_INVALID;
     return SURFHIP_OK;
 }
 
@@ -1275,6 +1278,26 @@ int surfhip_match_batch_guided(surfhip_point* pts1, const float* f1, const int* 
     const int bad = match_batch_args(b, kMatchBatchFlags | SURFHIP_MATCH_MUTUAL, MATCH_GUIDED, window, true, scratch);
     if (bad != SURFHIP_OK || npairs == 0) return bad;
     HIPCHK(launch_match_batch(b, MATCH_GUIDED, scratch, (hipStream_t)stream));
+    return SURFHIP_OK;
+}
+
+size_t surfhip_match_batch_epipolar_scratch(int npairs, int slots1, int slots2, int flags)
+{
+    return surfhip_match_batch_window_scratch(npairs, slots1, slots2, flags);
+}
+
+int surfhip_match_batch_epipolar(surfhip_point* pts1, const float* f1, const int* counts1, int slots1,
+                                 const surfhip_point* pts2, const float* f2, const int* counts2, int slots2,
+                                 int npairs, int nf, int flags, const float* f, int f_stride, float band,
+                                 const surfhip_match_window* window, void* scratch, void* stream)
+{
+    MatchBatch b = {pts1, f1, counts1, slots1, pts2, f2, counts2, slots2, npairs, nf, flags};
+    b.hm = f;
+    b.h_stride = f_stride;
+    b.band = band;
+    const int bad = match_batch_args(b, kMatchBatchFlags | SURFHIP_MATCH_MUTUAL, MATCH_EPIPOLAR, window, true, scratch);
+    if (bad != SURFHIP_OK || npairs == 0) return bad;
+    HIPCHK(launch_match_batch(b, MATCH_EPIPOLAR, scratch, (hipStream_t)stream));
     return SURFHIP_OK;
 }
 

@@ -280,13 +280,15 @@ hipError_t launch_match(surfhip_point* pts1, const surfhip_point* pts2, const fl
 // points / descriptors, counts on the device) against frame i of set 2.  The
 // point arrays may overlap (set 2 = set 1 advanced one frame).
 // What is offered to a set-1 point: every set-2 point, those in a window
-// around it, or those in a window around its predicted position.
-enum { MATCH_PLAIN = 0, MATCH_WINDOW = 1, MATCH_GUIDED = 2 };
+// around it, those in a window around its predicted position, or those in a
+// window around it that also lie in a band along its epipolar line.
+enum { MATCH_PLAIN = 0, MATCH_WINDOW = 1, MATCH_GUIDED = 2, MATCH_EPIPOLAR = 3 };
 // The arguments of a batched match, the kernels' too (by value).  The caller
-// fills the sets, npairs, nf, flags and, by mode, win (MATCH_WINDOW,
-// MATCH_GUIDED) and hm, h_stride (MATCH_GUIDED: pair i's 3 x 3 matrix is the
-// nine row-major floats at hm + i * h_stride in device memory, read in stream
-// order); launch_match_batch places back, boxes and tiles in its scratch.
+// fills the sets, npairs, nf, flags and, by mode, win (not MATCH_PLAIN), hm,
+// h_stride (MATCH_GUIDED, MATCH_EPIPOLAR: pair i's 3 x 3 matrix is the nine
+// row-major floats at hm + i * h_stride in device memory, read in stream
+// order) and band (MATCH_EPIPOLAR: the half width of the band, pixels);
+// launch_match_batch places back, boxes and tiles in its scratch.
 struct MatchBatch {
     surfhip_point* pts1;
     const float* f1;
@@ -303,6 +305,7 @@ struct MatchBatch {
     surfhip_match_window win;
     const float* hm;
     int h_stride;
+    float band;
     // the pairs from p0 on
     MatchBatch from(int p0) const
     {

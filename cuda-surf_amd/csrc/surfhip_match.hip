@@ -74,6 +74,21 @@
 // ahead of the tile loop, and from there on the prediction (u, v) stands where
 // the window kernels have (x1, y1) -- in the boxes, the kept-tile list and the
 // scan's test.
+//
+// Epipolar matching (surfhip_match_batch_epipolar) keeps the window around the
+// raw (x1, y1) and adds a band along the point's epipolar line under the
+// pair's fundamental matrix F: every set-1 point computes its line (a, b, c)
+// and lim = band^2 (a^2 + b^2) once, ahead of the tile loop, and the scan
+// offers (x2, y2) when r = (x2 a + y2 b) + c has r r <= lim -- no division, no
+// square root.  The tile boxes are the window call's; a line is tested against
+// a box through r at the box's four corners (every fp32 operation of r is
+// monotone in x2 and in y2, so r over the box lies between the smallest and
+// the largest corner value): a wave skips the MFMAs of a staged tile that
+// none of its lines can reach, and the block's kept-tile list drops a tile
+// that none of the block's lines can reach.  The boxes of detected keypoints
+// are wide and low (a band of rows over the frame's width), so this prunes
+// for lines that run along the rows -- a stereo rig; a steep line crosses
+// every such box and only the window prunes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -255,6 +270,49 @@ __device__ __forceinline__ void guided_predict(const float* __restrict__ m, floa
     v = front ? Y / W : __builtin_nanf("");
 }
 
+// A set-1 point's epipolar line under the row-major 3 x 3 matrix f, (x2, y2,
+// 1) f (x1, y1, 1)^T = 0, as (a, b, c) (the Sampson a, b, c of
+// surfhip_fundamental.hip), and lim = band^2 (a^2 + b^2): (x2, y2) lies within
+// band pixels of the line when r = (x2 a + y2 b) + c has r r <= lim.  One fp32
+// rounding per written operation; nothing is special-cased: an all-zero f
+// gives 0 <= 0 everywhere, a NaN in f a NaN lim, which no r r is below.
+struct EpiLine {
+    float a, b, c, lim;
+};
+
+__device__ __forceinline__ EpiLine epipolar_line(const float* __restrict__ f, float x, float y, float band)
+{
+    EpiLine l;
+    l.a = (f[0] * x + f[1] * y) + f[2];
+    l.b = (f[3] * x + f[4] * y) + f[5];
+    l.c = (f[6] * x + f[7] * y) + f[8];
+    l.lim = (band * band) * (l.a * l.a + l.b * l.b);
+    return l;
+}
+
+__device__ __forceinline__ bool epipolar_offered(const EpiLine& l, float x2, float y2)
+{
+    const float r = (x2 * l.a + y2 * l.b) + l.c;
+    return r * r <= l.lim;
+}
+
+// May the line offer a point of the box b = (xmin, xmax, ymin, ymax)?  Never
+// false for a box that holds an offered point: each operation of r is monotone
+// in x2 and in y2, so r over the box lies between the smallest and the largest
+// of its four corner values, computed with the same expression; squaring is
+// monotone on either side of 0.  So nothing is offered when all four corners
+// lie on one side of 0 with r r > lim.  A NaN corner or a NaN lim fails its
+// comparisons, which keeps the tile.
+__device__ __forceinline__ bool line_may_offer(const EpiLine& l, const float4& b)
+{
+    const float xa0 = b.x * l.a, xa1 = b.y * l.a, yb0 = b.z * l.b, yb1 = b.w * l.b;
+    const float r0 = (xa0 + yb0) + l.c, r1 = (xa1 + yb0) + l.c, r2 = (xa0 + yb1) + l.c, r3 = (xa1 + yb1) + l.c;
+    const bool far = r0 * r0 > l.lim && r1 * r1 > l.lim && r2 * r2 > l.lim && r3 * r3 > l.lim;
+    const bool above = r0 > 0.0f && r1 > 0.0f && r2 > 0.0f && r3 > 0.0f;
+    const bool below = r0 < 0.0f && r1 < 0.0f && r2 < 0.0f && r3 < 0.0f;
+    return !(far && (above || below));
+}
+
 // One 32 x 32 score tile D[p2][p1] into the lane's four row states: register
 // 4 q + r holds tile position 8 q + 4 h + r, i.e. thread row 2 q + h, r
 // ascending.  lap2: the laplace of tile position (lane & 31), LAP only.
@@ -266,14 +324,15 @@ __device__ __forceinline__ void guided_predict(const float* __restrict__ m, floa
 // 32 x then 32 y (16-B aligned), a lane reads its four positions of a q at
 // once; WIN_SHFL: x2, y2 are those of tile position (lane & 31).  A NaN
 // difference fails every comparison: not offered.
+// EPI (surfhip_match_batch_epipolar): and in the band along the lane's line ep.
 // (The kernels call it through scan_lane_tile, which has these in two structs:
 // with the structs read in here, or with cross_reduce behind the same call,
 // the CROSS kernels' registers are allocated differently.)
-template <bool LAP, bool CROSS, int WIN>
+template <bool LAP, bool CROSS, int WIN, bool EPI = false>
 __device__ __forceinline__ void scan_tile(const f32x16& acc, int t, int h, int nscan, int lap1, int lap2,
                                           float (&mx)[4], float (&sc)[4], int (&ix)[4], bool live1, uint32_t* ks,
                                           const surfhip_match_window* w, float x1, float y1, const float* xy2,
-                                          float x2, float y2)
+                                          float x2, float y2, const EpiLine* ep = nullptr)
 {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -294,9 +353,16 @@ __device__ __forceinline__ void scan_tile(const f32x16& acc, int t, int h, int n
             if constexpr (WIN != WIN_OFF) {
                 const float xr = r == 0 ? qx.x : r == 1 ? qx.y : r == 2 ? qx.z : qx.w;
                 const float yr = r == 0 ? qy.x : r == 1 ? qy.y : r == 2 ? qy.z : qy.w;
-                const float dx = (WIN == WIN_LDS ? xr : __shfl(x2, j)) - x1;
-                const float dy = (WIN == WIN_LDS ? yr : __shfl(y2, j)) - y1;
-                ok = ok && dx >= w->dx_min && dx <= w->dx_max && dy >= w->dy_min && dy <= w->dy_max;
+                if constexpr (!EPI) {
+                    const float dx = (WIN == WIN_LDS ? xr : __shfl(x2, j)) - x1;
+                    const float dy = (WIN == WIN_LDS ? yr : __shfl(y2, j)) - y1;
+                    ok = ok && dx >= w->dx_min && dx <= w->dx_max && dy >= w->dy_min && dy <= w->dy_max;
+                } else {
+                    const float xj = WIN == WIN_LDS ? xr : __shfl(x2, j), yj = WIN == WIN_LDS ? yr : __shfl(y2, j);
+                    const float dx = xj - x1, dy = yj - y1;
+                    ok = ok && dx >= w->dx_min && dx <= w->dx_max && dy >= w->dy_min && dy <= w->dy_max &&
+                         epipolar_offered(*ep, xj, yj);
+                }
             }
             if (ok) scan_update(acc[4 * q + r], p2, mx[q], sc[q], ix[q]);
             if constexpr (CROSS) {
@@ -384,6 +450,17 @@ __device__ __forceinline__ void scan_lane_tile(const f32x16& acc, int nscan, con
 {
     scan_tile<LAP, CROSS, WIN>(acc, tl.t, me.h, nscan, me.lap1, tl.lap2, mx, sc, ix, me.live1, ks, me.w, me.x1, me.y1,
                                tl.xy2, tl.x2, tl.y2);
+}
+
+// The same with the band along the lane's epipolar line (its own call: the
+// line inside ScanLane moves the registers of the kernels that have none).
+template <bool LAP, bool CROSS, int WIN>
+__device__ __forceinline__ void scan_lane_tile_epi(const f32x16& acc, int nscan, const ScanLane& me,
+                                                   const EpiLine& ln, const ScanTile& tl, float (&mx)[4],
+                                                   float (&sc)[4], int (&ix)[4], uint32_t* ks)
+{
+    scan_tile<LAP, CROSS, WIN, true>(acc, tl.t, me.h, nscan, me.lap1, tl.lap2, mx, sc, ix, me.live1, ks, me.w, me.x1,
+                                     me.y1, tl.xy2, tl.x2, tl.y2, &ln);
 }
 
 // Lanes l and l ^ 32 hold rows (0, 2, 4, 6) and (1, 3, 5, 7) of point p1;
@@ -476,10 +553,16 @@ __global__ __launch_bounds__(256) void k_match_tile_boxes(const MatchBatch mb)
 // no bit of the result depends on the skipping.
 // GUIDED (surfhip_match_batch_guided): WIN around the lane's prediction under
 // the pair's matrix, the nine floats at hm + pair * h_stride.
+// EPIPOLAR (surfhip_match_batch_epipolar): WIN around the raw point, and the
+// band along the lane's line under that matrix.  The block's lines lie in LDS;
+// the thread that tests a tile's box for the list also walks the lines of the
+// block's live points until one can reach the box, and a wave scores a staged
+// tile only when one of its own lines can.
 template <int NF, bool LAP, bool CROSS, int MODE = MATCH_PLAIN>
 __global__ __launch_bounds__(kBatchThreads) void k_match_batch(const MatchBatch mb)
 {
     constexpr bool WIN = MODE != MATCH_PLAIN;
+    constexpr bool EPI = MODE == MATCH_EPIPOLAR;
     constexpr int RS = NF + 4;                             // LDS row: NF / 2 even, NF / 2 odd elements, pad
     constexpr int C4 = NF / 4;                              // float4 per descriptor
     constexpr int NV = 32 * C4 / kBatchThreads;             // float4 per thread per tile
@@ -661,6 +744,17 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(const MatchBatch 
         const ScanLane me = {h, lap1, p1 < n1, x1, y1, &win};
         const float4 mybox = box_of_32(x1, y1, p1 < n1);    // the wave's live points (none: a dead wave)
         if (lane == 0) wbox[wave] = mybox;
+        // EPI: the lane's line (a lane past n1 has that of point n1 - 1, one of its
+        // wave's), and the block's lines, of which the first n1 - base are live
+        EpiLine ln = {0.0f, 0.0f, 0.0f, 0.0f};
+        const float4* lines = nullptr;
+        if constexpr (EPI) {
+            __shared__ float4 eline[kBatchPts];
+            ln = epipolar_line(mb.hm + (size_t)pair * mb.h_stride, x1, y1, mb.band);
+            if (h == 0) eline[32 * wave + c] = make_float4(ln.a, ln.b, ln.c, ln.lim);
+            lines = eline;
+        }
+        const int nline = min(kBatchPts, n1 - base);
         __syncthreads();
         float4 blockbox = wbox[0];
 #pragma unroll
@@ -671,7 +765,17 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(const MatchBatch 
             // tests tile t0 + tid, ballots and the waves' counts place it
             const int tt = t0 + tid;
             const float4 bb = boxes[min(tt, ntile - 1)];
-            const bool keep = tt < ntile && box_may_offer(blockbox, bb, win);
+            bool keep = tt < ntile && box_may_offer(blockbox, bb, win);
+            if constexpr (EPI) {
+                if (keep) {
+                    bool any = false;
+                    for (int k = 0; k < nline && !any; ++k) {
+                        const float4 l = lines[k];
+                        any = line_may_offer({l.x, l.y, l.z, l.w}, bb);
+                    }
+                    keep = any;
+                }
+            }
             const u64 kept = __ballot(keep);
             if (lane == 0) wcnt[wave] = __popcll(kept);
             __syncthreads();
@@ -709,10 +813,16 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(const MatchBatch 
                 }
                 // the wave's own box: a block over two (octave, level) groups is
                 // tall, its waves are not
-                if (wlive && __builtin_amdgcn_readfirstlane(box_may_offer(mybox, tbox[i], win))) {
+                bool mine = wlive && __builtin_amdgcn_readfirstlane(box_may_offer(mybox, tbox[i], win));
+                if constexpr (EPI) mine = mine && __ballot(line_may_offer(ln, tbox[i])) != 0;
+                if (mine) {
                     const f32x16 acc = score_tile(cur);
                     uint32_t ks[16];
-                    scan_lane_tile<LAP, CROSS, WIN_LDS>(acc, nscan, me, {t, lap2, xy2[cur]}, mx, sc, ix, ks);
+                    if constexpr (EPI)
+                        scan_lane_tile_epi<LAP, CROSS, WIN_LDS>(acc, nscan, me, ln, {t, lap2, xy2[cur]}, mx, sc, ix,
+                                                                ks);
+                    else
+                        scan_lane_tile<LAP, CROSS, WIN_LDS>(acc, nscan, me, {t, lap2, xy2[cur]}, mx, sc, ix, ks);
                     if constexpr (CROSS) {
                         int j;
                         const u64 key = cross_reduce(ks, p1, h, c, j);
@@ -739,10 +849,12 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch(const MatchBatch 
 // CROSS: every wave sends its own 32 keys per tile.
 // WIN: a wave walks all tile boxes and skips the tiles its own box misses.
 // GUIDED: as in k_match_batch.
+// EPIPOLAR: ... and the tiles none of its own lines can reach.
 template <bool LAP, bool CROSS, int MODE = MATCH_PLAIN>
 __global__ __launch_bounds__(kBatchThreads) void k_match_batch_any(const MatchBatch mb)
 {
     constexpr bool WIN = MODE != MATCH_PLAIN;
+    constexpr bool EPI = MODE == MATCH_EPIPOLAR;
     const int pair = blockIdx.y, slots1 = mb.slots1, slots2 = mb.slots2, nf = mb.nf;
     const int* __restrict__ counts1 = mb.counts1;
     const int* __restrict__ counts2 = mb.counts2;
@@ -782,11 +894,16 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch_any(const MatchBa
         if constexpr (MODE == MATCH_GUIDED) guided_predict(mb.hm + (size_t)pair * mb.h_stride, x1, y1, x1, y1);
         mybox = box_of_32(x1, y1, p1 < n1);
     }
+    EpiLine ln = {0.0f, 0.0f, 0.0f, 0.0f};
+    if constexpr (EPI) ln = epipolar_line(mb.hm + (size_t)pair * mb.h_stride, x1, y1, mb.band);
     const ScanLane me = {h, lap1, p1 < n1, x1, y1, &win};
     constexpr int W = WIN ? WIN_SHFL : WIN_OFF;
     for (int t = 0; t < ntile; ++t) {
         if constexpr (WIN) {
             if (!__builtin_amdgcn_readfirstlane(box_may_offer(mybox, boxes[t], win))) continue;
+        }
+        if constexpr (EPI) {
+            if (__ballot(line_may_offer(ln, boxes[t])) == 0) continue;
         }
         const int q2 = min(32 * t + c, nscan - 1);
         const float* r2 = f2 + (size_t)q2 * nf + h;
@@ -795,7 +912,10 @@ __global__ __launch_bounds__(kBatchThreads) void k_match_batch_any(const MatchBa
         f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         for (int d = 0; d < nf; d += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(r2[d], r1[d], acc, 0, 0, 0);
         uint32_t ks[16];
-        scan_lane_tile<LAP, CROSS, W>(acc, nscan, me, {t, lap2, nullptr, x2, y2}, mx, sc, ix, ks);
+        if constexpr (EPI)
+            scan_lane_tile_epi<LAP, CROSS, W>(acc, nscan, me, ln, {t, lap2, nullptr, x2, y2}, mx, sc, ix, ks);
+        else
+            scan_lane_tile<LAP, CROSS, W>(acc, nscan, me, {t, lap2, nullptr, x2, y2}, mx, sc, ix, ks);
         if constexpr (CROSS) {
             int j;
             const u64 key = cross_reduce(ks, p1, h, c, j);
@@ -868,7 +988,8 @@ static BatchKernel batch_kernel(int mode, bool cross, bool lap, int nf)
     if constexpr (MODE < 0)
         return mode == MATCH_PLAIN    ? batch_kernel<MATCH_PLAIN>(mode, cross, lap, nf)
                : mode == MATCH_WINDOW ? batch_kernel<MATCH_WINDOW>(mode, cross, lap, nf)
-                                      : batch_kernel<MATCH_GUIDED>(mode, cross, lap, nf);
+               : mode == MATCH_GUIDED ? batch_kernel<MATCH_GUIDED>(mode, cross, lap, nf)
+                                      : batch_kernel<MATCH_EPIPOLAR>(mode, cross, lap, nf);
     else if constexpr (CROSS < 0)
         return cross ? batch_kernel<MODE, 1>(mode, cross, lap, nf) : batch_kernel<MODE, 0>(mode, cross, lap, nf);
     else if constexpr (LAP < 0)

@@ -482,7 +482,7 @@ int surfhip_match_batch_cross(surfhip_point* d_pts1, const float* d_desc1, const
  * npairs > 0; otherwise npairs == 0 returns SURFHIP_OK without touching the
  * GPU. */
 typedef struct surfhip_match_window { float dx_min, dx_max, dy_min, dy_max; } surfhip_match_window;
-#define SURFHIP_MATCH_MUTUAL 4   /* surfhip_match_batch_window and _guided only */
+#define SURFHIP_MATCH_MUTUAL 4   /* surfhip_match_batch_window, _guided, _epipolar */
 size_t surfhip_match_batch_window_scratch(int npairs, int slots1, int slots2, int flags);
 int surfhip_match_batch_window(surfhip_point* d_pts1, const float* d_desc1, const int* d_counts1, int slots1,
                                const surfhip_point* d_pts2, const float* d_desc2, const int* d_counts2, int slots2,
@@ -663,6 +663,74 @@ int surfhip_fundamental_batch(const surfhip_point* d_pts1, const int* d_counts1,
 /* Candidates per pair the kernel keeps in LDS; pairs with more are still
  * exact, the rest is re-read from the point array. */
 int surfhip_fundamental_lds_capacity(void);
+
+/* Epipolar matching: surfhip_match_batch_window with, beside the window, a
+ * band along each set-1 point's epipolar line under a per-pair fundamental
+ * matrix -- the second pass of a stereo rig or of a camera that translates:
+ * match -> surfhip_fundamental_batch -> epipolar match, with the matrices
+ * never leaving the device.  The best partner on the line may be the third
+ * best overall, so this cannot be had by filtering the matches of a plain
+ * call.  Layouts, count clamping, flags (SURFHIP_MATCH_FULL_TAIL |
+ * SURFHIP_MATCH_SAME_LAPLACE | SURFHIP_MATCH_MUTUAL), the nfeatures rule, the
+ * overlap rule for consecutive frames and the scratch (layout and size:
+ * surfhip_match_batch_epipolar_scratch returns the numbers of
+ * surfhip_match_batch_window_scratch) are those of surfhip_match_batch_window.
+ * d_f: device memory, 4-byte aligned, read on the device in stream order, so
+ * the output of a surfhip_fundamental_batch enqueued earlier on the same
+ * stream can be passed directly.  Pair i uses the nine row-major floats at
+ * d_f + i * f_stride, f_stride in floats: 16 for an array of
+ * surfhip_fundamental (f is its first member; nothing else of the record is
+ * read, not even status), 9 for packed matrices, any value >= 9, or 0 for one
+ * matrix shared by all pairs.  F has the convention of
+ * surfhip_fundamental_batch: (x2, y2, 1) F (x1, y1, 1)^T = 0.
+ * Set-2 point p2 is offered to set-1 point p1 when
+ *   p2 < nscan,
+ *   with SURFHIP_MATCH_SAME_LAPLACE their `laplace` fields are equal,
+ *   dx_min <= x2 - x1 <= dx_max and dy_min <= y2 - y1 <= dy_max around the raw
+ *   (x1, y1), as in surfhip_match_batch_window (the infinite window switches
+ *   this off; a stereo caller puts the disparity range here), and
+ *   (x2, y2) lies within `band` pixels of p1's epipolar line, tested squared
+ *   and cross-multiplied, every written operation one fp32 rounding:
+ *     a = (f0*x1 + f1*y1) + f2;  b = (f3*x1 + f4*y1) + f5;  c = (f6*x1 + f7*y1) + f8;
+ *     lim = (band * band) * (a*a + b*b);
+ *     r = (x2*a + y2*b) + c;     offered  <=>  r*r <= lim
+ *   (inclusive; any NaN: not offered).  a, b, c are the Sampson a, b, c above.
+ * Forward, back direction and SURFHIP_MATCH_MUTUAL clearing are those of
+ * surfhip_match_batch_window over this "offered"; only the five match fields
+ * of set-1 points below n1 are written.  There is no special case for a
+ * degenerate line; the arithmetic as written decides:
+ *   An all-zero matrix (what a TOO_FEW / DEGENERATE surfhip_fundamental holds)
+ *   gives, for finite coordinates, a = b = c = r = lim = 0 and 0 <= 0: the
+ *   result is, bit for bit, that of surfhip_match_batch_window with the same
+ *   window and flags -- a failed F degrades to the plain window, as a failed
+ *   homography does in the guided call.
+ *   The rectified matrix (0,0,0, 0,0,-1, 0,1,0) gives a = 0, b = -1, c = y1 and
+ *   r = -(y2 - y1) exactly: with the window (dx_min, dx_max, -inf, +inf) and
+ *   band B the result is, bit for bit, that of surfhip_match_batch_window
+ *   with (dx_min, dx_max, -B, B), for finite coordinates and a B with
+ *   |d| <= B <=> d*d <= B*B in fp32 (1.5, say).
+ *   A matrix that holds a NaN offers nothing: its pair's points get
+ *   match = -1 and zeros.
+ * band = 0 is valid: only r*r == 0 is offered.
+ * The tile skipping of the window call applies as it is, and a 32 x 32 score
+ * tile is also skipped when none of its set-1 points' lines can come within
+ * the band of the tile's bounding box (r at the box's four corners bounds r
+ * over the box; a NaN keeps the tile).  That changes no bit of the result.
+ * The boxes of surfhip_detect_batch's point order are bands of rows, so the
+ * line test prunes for lines that run along the rows (stereo); for steep
+ * lines only the window prunes.  Asynchronous on `stream`, no host
+ * synchronisation, no allocation.  SURFHIP_ERR_INVALID for everything
+ * surfhip_match_batch_window rejects, for an f_stride that is neither 0 nor
+ * >= 9 and for a band that is NaN, infinite or negative -- these for
+ * npairs == 0 too -- and for a NULL or misaligned d_f or d_scratch with
+ * npairs > 0; otherwise npairs == 0 returns SURFHIP_OK without touching the
+ * GPU. */
+size_t surfhip_match_batch_epipolar_scratch(int npairs, int slots1, int slots2, int flags);
+int surfhip_match_batch_epipolar(surfhip_point* d_pts1, const float* d_desc1, const int* d_counts1, int slots1,
+                                 const surfhip_point* d_pts2, const float* d_desc2, const int* d_counts2, int slots2,
+                                 int npairs, int nfeatures, int flags,
+                                 const float* d_f, int f_stride, float band,
+                                 const surfhip_match_window* window, void* d_scratch, void* stream);
 
 /* ------------------------------------------------------------- ingest --
  * Pipelined host-frame ingest.  Replaces the

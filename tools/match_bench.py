@@ -45,6 +45,22 @@ prints times, matches (and how many are the true partner) and the kept (block,
 tile) and (wave, tile) shares of both.  --cross adds SURFHIP_MATCH_MUTUAL.
 
     python tools/match_bench.py --guided 32 [--cross] [--reps 7] [--inner 4]
+
+--epipolar B times surfhip_match_batch_epipolar with a band of B px on the same
+detected frames, all calls alternating in one run.  (1) The 255 consecutive
+pairs: the all-zero matrix with the window +-32 px against
+surfhip_match_batch_window with +-32 px; the two must write the same bytes
+(exit status 1 if not).  (2) Rectified stereo: set 2 is each frame's own
+keypoints moved by a per-point disparity in [-64, 0] px along their row
+(re-sorted as for --guided): the epipolar call with the rectified matrix and
+the window (-64, 0, -inf, inf) against the window call with (-64, 0, -B, B);
+the same bytes again.  (3) The same disparities along lines tilted by 3
+degrees: the epipolar call under that matrix against the window call opened
+just tall enough to hold every true partner.  It prints times, matches (and how
+many are the true partner) and the kept (block, tile) and (wave, tile) shares,
+computed in numpy.  --cross adds SURFHIP_MATCH_MUTUAL.
+
+    python tools/match_bench.py --epipolar 1.5 [--cross] [--reps 7] [--inner 4]
 """
 from __future__ import annotations
 
@@ -184,9 +200,12 @@ def kept_tile_shares(surf, pts, counts, win):
     return kept_pair_shares(pts[:-1], counts[:-1], pts[1:], counts[1:], win)
 
 
-def kept_pair_shares(pts1, counts1, pts2, counts2, win):
+def kept_pair_shares(pts1, counts1, pts2, counts2, win, f=None, band=0.0):
     """The same for pair i = pts1[i] (its x, y: the positions the window is
-    measured from) against pts2[i]."""
+    measured from) against pts2[i].  f, band: the matrix and band of
+    surfhip_match_batch_epipolar, whose kernels also drop a combination when
+    none of the group's epipolar lines can come within the band of the tile's
+    box (r at the box's four corners, fp32)."""
     w = np.asarray(win, np.float32)
     inf = np.float32(np.inf)
 
@@ -211,9 +230,42 @@ def kept_pair_shares(pts1, counts1, pts2, counts2, win):
             with np.errstate(invalid="ignore"):
                 keep = (~(b[0][None] - a[1][:, None] > w[1]) & ~(b[1][None] - a[0][:, None] < w[0])
                         & ~(b[2][None] - a[3][:, None] > w[3]) & ~(b[3][None] - a[2][:, None] < w[2]))
+            if f is not None:
+                keep &= lines_reach(pts1[i], n1, group, b, f, band)
             tot[group] += keep.size
             kept[group] += int(keep.sum())
     return kept[128] / max(tot[128], 1), kept[32] / max(tot[32], 1)
+
+
+def epipolar_lines_f32(f, band, x, y):
+    """surfhip_match_batch_epipolar's (a, b, c, lim) of the set-1 points, its
+    fp32 operations."""
+    f = np.asarray(f, np.float32)
+    bb = np.float32(band) * np.float32(band)
+    with np.errstate(all="ignore"):
+        a = (f[0] * x + f[1] * y) + f[2]
+        b = (f[3] * x + f[4] * y) + f[5]
+        c = (f[6] * x + f[7] * y) + f[8]
+        return a, b, c, bb * (a * a + b * b)
+
+
+def lines_reach(p, n, group, boxes, f, band):
+    """[groups of `group` set-1 points][tiles]: one of the group's lines may
+    offer a point of the tile's box (xmin, xmax, ymin, ymax arrays): not all
+    four corner values of r on one side of 0 with r r > lim."""
+    g = (n + group - 1) // group
+    x = np.zeros(g * group, np.float32)
+    y = np.zeros(g * group, np.float32)
+    x[:n], y[:n] = p["x"][:n], p["y"][:n]
+    live = (np.arange(g * group) < n).reshape(g, group, 1)
+    a, b, c, lim = (v.reshape(g, group, 1) for v in epipolar_lines_f32(f, band, x, y))
+    with np.errstate(all="ignore"):
+        xa = [boxes[0][None, None, :] * a, boxes[1][None, None, :] * a]
+        yb = [boxes[2][None, None, :] * b, boxes[3][None, None, :] * b]
+        rs = [(xa[i] + yb[j]) + c for j in (0, 1) for i in (0, 1)]
+        far = np.logical_and.reduce([r * r > lim for r in rs])
+        side = np.logical_and.reduce([r > 0 for r in rs]) | np.logical_and.reduce([r < 0 for r in rs])
+    return (~(far & side) & live).any(axis=1)
 
 
 def bench_window(surf, torch, radius, cross, frames_n, reps, inner, width=1920, height=1080, thresh=4.0,
@@ -316,14 +368,21 @@ def moved_set(pts, counts, h64, height, init_sample=2):
     octave changes or y falls by more than a quarter of the frame height; a
     row is the octave's sampling step, init_sample << octave, of the new y.
     Returns (moved points, perm) with moved[i, j] = map(pts[i, perm[i, j]])."""
+    def through(x, y):
+        w = h64[2, 0] * x + h64[2, 1] * y + h64[2, 2]
+        return (h64[0, 0] * x + h64[0, 1] * y + h64[0, 2]) / w, (h64[1, 0] * x + h64[1, 1] * y + h64[1, 2]) / w
+
+    return moved_by(pts, counts, lambda i, x, y: through(x, y), height, init_sample)
+
+
+def moved_by(pts, counts, move, height, init_sample=2):
+    """moved_set for any map: move(i, x, y) gives frame i's new fp64
+    coordinates."""
     moved = pts.copy()
     perm = np.tile(np.arange(pts.shape[1]), (len(pts), 1))
     for i, n in enumerate(counts):
         p = pts[i, :n]
-        x, y = p["x"].astype(np.float64), p["y"].astype(np.float64)
-        w = h64[2, 0] * x + h64[2, 1] * y + h64[2, 2]
-        mx = ((h64[0, 0] * x + h64[0, 1] * y + h64[0, 2]) / w).astype(np.float32)
-        my = ((h64[1, 0] * x + h64[1, 1] * y + h64[1, 2]) / w).astype(np.float32)
+        mx, my = (v.astype(np.float32) for v in move(i, p["x"].astype(np.float64), p["y"].astype(np.float64)))
         start = np.zeros(n, bool)
         start[1:] = (p["o"][1:] != p["o"][:-1]) | (p["y"][1:] < p["y"][:-1] - 0.25 * height)
         group = np.cumsum(start)
@@ -442,6 +501,135 @@ def bench_guided(surf, torch, radius, cross, frames_n, reps, inner, width=1920, 
         raise SystemExit("surfhip_match_batch_guided with the identity disagrees with surfhip_match_batch_window")
 
 
+def bench_epipolar(surf, torch, band, cross, frames_n, reps, inner, width=1920, height=1080, thresh=4.0, slots=8192,
+                   radius=32.0, disparity=64.0, tilt_deg=3.0):
+    """surfhip_match_batch_epipolar against surfhip_match_batch_window, all six
+    calls alternating in one run on one detected batch of synthetic frames
+    (see the module docstring): the zero matrix (the same bytes: the cost of
+    the mode itself), rectified stereo (the same bytes: the cost of the line
+    test and the list build on the same offered set) and tilted lines (what
+    only this call can prune)."""
+    dev = torch.device("cuda", 0)
+    surf.set_device(0)
+    B, npairs = frames_n, frames_n - 1
+    pitch = surf.align_up(width, 128)
+    d_frames = torch.from_numpy(surf.synth_frames(B, width, height, pitch)).to(dev)
+    param = surf.make_param(4, thresh, False, 9, 2, True, False, 4)
+    nf = param.nfeatures
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    det = surf.Detector(param, width, height, max_batch=B, max_pts=slots, stream=stream)
+    d_pts = torch.zeros(B * slots * 48, dtype=torch.uint8, device=dev)
+    d_desc = torch.empty(B * slots * nf, dtype=torch.float32, device=dev)
+    d_cnt = torch.zeros(B, dtype=torch.int32, device=dev)
+    det.detect_batch(d_frames.data_ptr(), B, pitch, height * pitch, d_pts.data_ptr(), d_desc.data_ptr(),
+                     d_cnt.data_ptr())
+    torch.cuda.synchronize()
+    flags = surf.MATCH_MUTUAL if cross else 0
+    d_scratch = torch.empty(max(surf.match_batch_epipolar_scratch_bytes(npairs, slots, slots, flags), 16),
+                            dtype=torch.uint8, device=dev)
+    counts = d_cnt.cpu().numpy()
+    pts = d_pts.cpu().numpy().view(surf.POINT_DTYPE).reshape(B, slots).copy()
+    live = np.arange(slots)[None, :] < counts[:npairs, None]
+    inf = float("inf")
+
+    # the stereo sets: a disparity per point, along its row and along a line tilted by tilt_deg
+    rng = np.random.default_rng(2024)
+    disp = [-disparity * rng.random(int(n)) for n in counts[:npairs]]
+    slope = float(np.float32(np.tan(np.radians(tilt_deg))))
+    f_zero = np.zeros(9, np.float32)
+    f_rect = np.array([0, 0, 0, 0, 0, -1, 0, 1, 0], np.float32)
+    f_tilt = np.array([0, 0, slope, 0, 0, -1, -slope, 1, 0], np.float32)      # y2 - y1 = slope (x2 - x1)
+    sets2 = {}
+    for name, k in (("rect", 0.0), ("tilt", slope)):
+        moved, perm = moved_by(pts[:npairs], counts[:npairs], lambda i, x, y: (x + disp[i], y + k * disp[i]), height)
+        back = np.argsort(perm, axis=1)                            # set-1 point k lies at set-2 index back[i, k]
+        d_perm = torch.from_numpy(perm).to(dev)
+        sets2[name] = (moved, back, torch.from_numpy(moved.view(np.uint8).reshape(-1)).to(dev),
+                       torch.take_along_dim(d_desc.view(B, slots, nf)[:npairs], d_perm[:, :, None], dim=1).contiguous())
+    with np.errstate(invalid="ignore"):
+        moved, back = sets2["tilt"][:2]
+        ty = np.take_along_axis(moved["y"], back, axis=1) - pts[:npairs]["y"]       # one fp32 subtraction, as the call's
+    tall = (-disparity, 0.0, float(ty[live].min()), float(ty[live].max()))
+    tight = (-radius, radius, -radius, radius)
+    rows = (-disparity, 0.0, -band, band)
+    open_y = (-disparity, 0.0, -inf, inf)
+    d_f = torch.from_numpy(np.concatenate([f_zero, f_rect, f_tilt])).to(dev)
+    d_out = torch.zeros(npairs * slots * 48, dtype=torch.uint8, device=dev)          # set 1 of the stereo calls
+
+    consecutive = (d_pts.data_ptr(), d_desc.data_ptr(), d_cnt.data_ptr(), slots,
+                   d_pts.data_ptr() + 48 * slots, d_desc.data_ptr() + 4 * slots * nf, d_cnt.data_ptr() + 4, slots)
+
+    def stereo(name):
+        return (d_out.data_ptr(), d_desc.data_ptr(), d_cnt.data_ptr(), slots,
+                sets2[name][2].data_ptr(), sets2[name][3].data_ptr(), d_cnt.data_ptr(), slots)
+
+    sp, fp = d_scratch.data_ptr(), d_f.data_ptr()
+    calls = {
+        "window": lambda: surf.match_batch_window(*consecutive, npairs, nf, flags, tight, sp, stream),
+        "epipolar_zero": lambda: surf.match_batch_epipolar(*consecutive, npairs, nf, flags, fp, 0, band, tight, sp,
+                                                           stream),
+        "window_rows": lambda: surf.match_batch_window(*stereo("rect"), npairs, nf, flags, rows, sp, stream),
+        "epipolar_rect": lambda: surf.match_batch_epipolar(*stereo("rect"), npairs, nf, flags, fp + 36, 0, band,
+                                                           open_y, sp, stream),
+        "window_tall": lambda: surf.match_batch_window(*stereo("tilt"), npairs, nf, flags, tall, sp, stream),
+        "epipolar_tilt": lambda: surf.match_batch_epipolar(*stereo("tilt"), npairs, nf, flags, fp + 72, 0, band,
+                                                           open_y, sp, stream),
+    }
+    out = {}
+    for name, fn in calls.items():                  # warm-up, and the results to compare
+        on_out = name not in ("window", "epipolar_zero")
+        if on_out:
+            d_out.copy_(d_pts[:npairs * slots * 48])
+        fn()
+        torch.cuda.synchronize()
+        out[name] = (d_out if on_out else d_pts).cpu().numpy().view(surf.POINT_DTYPE).reshape(-1, slots)[:npairs].copy()
+    same_zero = out["window"].tobytes() == out["epipolar_zero"].tobytes()
+    same_rect = out["window_rows"].tobytes() == out["epipolar_rect"].tobytes()
+    times = {name: [] for name in calls}
+    for _ in range(reps):                           # the calls alternate inside one run
+        for name, fn in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(inner):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1) / inner)
+    res = {"case": f"{npairs} pairs of {B} {width}x{height} frames, nf={nf} flags={flags}, epipolar band {band} px"
+                   + (", mutual-best" if cross else ""),
+           "reps": reps, "inner": inner, "keypoints_mean": round(float(counts.mean()), 1),
+           "set1_points": int(live.sum()), "zero_matrix_bit_identical": same_zero,
+           "rectified_bit_identical": same_rect, "tilt_deg": tilt_deg, "tall_window": [round(v, 3) for v in tall]}
+    for name, t in times.items():
+        res[f"{name}_ms"] = round(float(np.median(t)), 4)
+        res[f"{name}_ms_range"] = [round(min(t), 4), round(max(t), 4)]
+    res["epipolar_zero_over_window"] = round(res["epipolar_zero_ms"] / res["window_ms"], 4)
+    res["epipolar_rect_over_window_rows"] = round(res["epipolar_rect_ms"] / res["window_rows_ms"], 4)
+    res["epipolar_tilt_over_window_tall"] = round(res["epipolar_tilt_ms"] / res["window_tall_ms"], 4)
+    p1 = pts[:npairs]
+    shares = {"window": (p1, pts[1:], counts[1:], tight, None),
+              "epipolar_zero": (p1, pts[1:], counts[1:], tight, f_zero),
+              "window_rows": (p1, sets2["rect"][0], counts[:npairs], rows, None),
+              "epipolar_rect": (p1, sets2["rect"][0], counts[:npairs], open_y, f_rect),
+              "window_tall": (p1, sets2["tilt"][0], counts[:npairs], tall, None),
+              "epipolar_tilt": (p1, sets2["tilt"][0], counts[:npairs], open_y, f_tilt)}
+    for name, (a, b, c2, win, f) in shares.items():
+        m = out[name]["match"]
+        res[f"matches_{name}"] = int((m[live] >= 0).sum())
+        if name not in ("window", "epipolar_zero"):
+            back = sets2["rect" if name in ("window_rows", "epipolar_rect") else "tilt"][1]
+            res[f"true_partner_{name}"] = int((m[live] == back[live]).sum())
+        block_share, wave_share = kept_pair_shares(a, counts[:npairs], b, c2, win, f, band)
+        res[f"kept_block_tile_share_{name}"] = round(block_share, 4)
+        res[f"kept_wave_tile_share_{name}"] = round(wave_share, 4)
+    print(json.dumps(res), flush=True)
+    det.close()
+    if not same_zero:
+        raise SystemExit("surfhip_match_batch_epipolar with the zero matrix disagrees with surfhip_match_batch_window")
+    if not same_rect:
+        raise SystemExit("surfhip_match_batch_epipolar with the rectified matrix disagrees with the window of rows")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=3000)
@@ -456,10 +644,17 @@ def main():
                     help="time surfhip_match_batch_window with +-R px on detected frames (--cross: with MUTUAL)")
     ap.add_argument("--guided", type=float, default=0.0, metavar="R",
                     help="time surfhip_match_batch_guided with +-R px against the window call (--cross: with MUTUAL)")
-    ap.add_argument("--frames", type=int, default=256, help="--window, --guided: synthetic 1920x1080 frames to detect")
+    ap.add_argument("--epipolar", type=float, default=0.0, metavar="B",
+                    help="time surfhip_match_batch_epipolar with a band of B px against the window call "
+                         "(--cross: with MUTUAL)")
+    ap.add_argument("--frames", type=int, default=256,
+                    help="--window, --guided, --epipolar: synthetic 1920x1080 frames to detect")
     args = ap.parse_args()
     import torch
     surf = load_surf()
+    if args.epipolar > 0:
+        bench_epipolar(surf, torch, args.epipolar, args.cross, args.frames, args.reps, args.inner)
+        return
     if args.guided > 0:
         bench_guided(surf, torch, args.guided, args.cross, args.frames, args.reps, args.inner)
         return
